@@ -11,9 +11,17 @@ bracketed by barrier + synchronize; the max time over ranks is used. Prints ONE 
 ``roofline``: the dominant kernel is ``zb_step_kernel``; its per-launch time is measured in this
 process with hipEvents on the launch stream (libzbot ``zb_profile_begin/end``). Algorithmic bytes
 per env-step = 946 B: 87 fp32 persistent state read + written, the 16-float
-self-contact cache read + written (128 B), actions 24 B, obs 92 B, reward 4 B, two flag bytes. ``cpu_baseline``: the C oracle (same model + algorithm,
-OpenMP over envs) on all of this host's cores available to the process and on one thread, on a
-bounded sample, with nproc / affinity / cgroup quota / CPU model stated.
+self-contact cache read + written (128 B), actions 24 B, obs 92 B, reward 4 B, two flag bytes.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the line.
+``--full`` adds the legs that take time of their own. ``cpu_baseline`` (null without ``--full``): the
+C oracle (same model + algorithm, OpenMP over envs) on all of this host's cores available to the
+process and on one thread, on a bounded sample, with nproc / affinity / cgroup quota / CPU model
+stated.
+
+``--dump-outputs DIR``: after the timed steps, what the last timed ``step()`` returned (obs, reward,
+terminated, truncated) is written as float32 ``DIR/<name>.npy``. Envs, resets and actions are all
+seeded, so two builds run with the same arguments receive identical inputs.
 
 ``--task v4`` measures zbot-6b-walking-v4 (commands / events / curricula; ``zb_v4_step_kernel``, 918 B
 per env-step: 81 state rows read, 85 written, actions, obs 96 B, reward, flags, the contact cache) at
@@ -57,8 +65,13 @@ def parse():
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--task", choices=("walking", "standup", "v4", "manager"), default="walking")
     p.add_argument("--envs-per-gpu", type=int, default=None, help="default 4096 (walking) / 32768 (standup, C5)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure (the CPU baseline); a plain run sets up, "
+                        "warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step() returned as DIR/<name>.npy (float32)")
     p.add_argument("--cpu-baseline-seconds", type=float, default=20.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     p.add_argument("--event-stride", type=int, default=8,
                    help="the roofline's kernel time: HIP start / stop events on every N-th timed step launch (the "
                         "event dispatch adds ~5.7 us to the step it brackets: 1 = every step, 4.3 %% slower)")
@@ -273,6 +286,29 @@ def init_group(plan: dict, dist_mod=None):
     return dist_mod
 
 
+DUMP_MAX_BYTES = 60_000_000   # array data; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(out_dir: str, step_out, rank: int = 0, world: int = 1) -> None:
+    """Write what ``env.step()`` returned (obs["policy"], reward, terminated, truncated; the extras dict is
+    the episode log, not a per-step output) as float32 ``<name>.npy`` under ``out_dir`` (``<name>_rank<r>.npy``
+    with more than one rank). Outputs past 60 MB in all are cut to a fixed, seeded sample of env rows."""
+    import numpy as np
+    obs, rew, term, trunc = step_out[:4]
+    arrs = {"obs_policy": obs["policy"], "reward": rew, "terminated": term, "truncated": trunc}
+    arrs = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrs.items()}
+    n = len(arrs["reward"])
+    row_bytes = sum(a.nbytes for a in arrs.values()) // max(n, 1)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (row_bytes + 8), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["env_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}{sfx}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     cmd = launch_plan(args.gpus, os.environ, sys.argv[1:])
@@ -322,11 +358,14 @@ def main():
     env.sim.profile_begin(args.steps, stride=max(1, args.event_stride))
     barrier()
     t0 = time.perf_counter()
+    last = None
     for k in range(args.steps):
-        env.step(pool[k % len(pool)])
+        last = env.step(pool[k % len(pool)])
     barrier()
     elapsed = time.perf_counter() - t0
     kern_ms, kern_n = env.sim.profile_end()
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, last, rank, world)
 
     rdev = plan["reduce_device"]  # (gloo reduces host tensors)
     t = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
@@ -389,7 +428,7 @@ def main():
                          "valu": valu_roofline(n, kern_s, kname)},
             "cpu_baseline": None,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(min(n, 4096), args.cpu_baseline_seconds, args.task)
         print(json.dumps(out), flush=True)
     env.close()

@@ -4,7 +4,7 @@
 # Every step runs under its own time limit, writes gpurun_out/<tag>/<step>.log and stops the call on
 # the first failure (no GPU step starts after a fault, an abort or a time limit). Steps:
 #   suite            pytest -m gpu (the driver's suite) + smoke()
-#   bench            the default bench line (4096 envs, with the CPU leg)
+#   bench            the default bench line (4096 envs) with --full (the CPU leg)
 #   lines            bench lines: 4096 / 8192 / 65536 envs and the other tasks (no CPU leg)
 #   solver           bench lines at solver modes $MODES (0 3) x self_manifold $SMS (2 3) x $SIZES envs
 #   prof             rocprofv3 kernel trace + stats, then separate PMC passes, on bench.py; writes
@@ -39,7 +39,7 @@ for s in "$@"; do
       run test_gpu 900 $PT tests -m gpu
       run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     bench)
-      run bench 400 python bench.py ;;
+      run bench 400 python bench.py --full ;;
     lines)
       for n in 4096 8192 65536; do run bench_$n 300 python bench.py --envs-per-gpu $n --no-cpu-baseline; done
       for t in standup v4 manager; do run bench_$t 300 python bench.py --task $t --no-cpu-baseline; done ;;

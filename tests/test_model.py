@@ -8,11 +8,11 @@ from __future__ import annotations
 import os
 
 import numpy as np
-import pytest
 
 from zbot_lab_amd import model as zm
 
-REF_USD = "/root/reference/source/zbot/zbot/assets/zbot_assets/zbot_6s_new.usd"
+# the reference's robot asset (zbot/assets/zbot_assets/zbot_6s_new.usd), stored as a fixture
+REF_USD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "zbot_6s_new.usd")
 
 
 def test_fk_known_answers(robot):
@@ -79,7 +79,6 @@ def test_pack_roundtrip(robot):
     assert c.max_episode_length == 1000 and abs(c.reward_scales[5] - 0.1) < 1e-7   # step_length 5 * 0.02
 
 
-@pytest.mark.skipif(not os.path.exists(REF_USD), reason="reference asset not present (GPU box)")
 def test_usdc_decoder_known_answers():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(__file__)), "tools"))
