@@ -371,6 +371,12 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
 /* Observation of the current state (v2.py:351-365), as reset() returns. obs: float[N][23]. */
 int zb_observe(zb_handle h, float* obs, void* stream);
 
+/* Which step-kernel instantiation the next zb_step launches: out = {kTgs, kOcc, kRefresh, kRf}, the
+ * template arguments of the task's step kernel (solver_mode >= 1; 1 / 2 waves per SIMD, from
+ * num_envs <= 4096 and ZB_OCC1; solver_mode >= 2; self_manifold 3 -- the last two always 0 for
+ * walking v4 and the manager task, whose kernels do not have them). Host only, no HIP call. */
+int zb_kernel_variant(zb_handle h, int32_t out[4]);
+
 /* Episode log of the most recent step with resets: term_means[ZB_LOG_LEN] (layout at
  * ZB_LOG_LEN; walking v2: mean episodic sum / 20 s, standup / v4: mean of sum / own duration),
  * counts[ZB_LOG_COUNTS] (layout at ZB_LOG_COUNTS; v2.py:441-459). Device pointers. */

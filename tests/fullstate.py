@@ -33,12 +33,60 @@ SOLVER_MODE = 0  # zb_task_cfg.solver_mode of the configs below (tests switch it
 SELF_MANIFOLD = None  # zb_task_cfg.self_manifold override (tests switch it with self_manifold())
 
 
-def task_cfg(task: str) -> zm.TaskCfg:
-    cfg = {"v2": zm.TaskCfg, "v4": zm.TaskCfg.walking_v4, "standup": zm.TaskCfg.standup,
-           "manager": zm.TaskCfg.manager_flat}[base_task(task)]()
+PRODUCT = False  # task_cfg() returns product_cfg() (tests switch it with product())
+
+# the registered env of each task (zbot_lab_amd.tasks): its cfg is what the product runs
+ENV_IDS = {"v2": "zbot-6b-walking-v2", "v4": "zbot-6b-walking-v4", "standup": "zbot-6b-standup-v0",
+           "manager": "zbot-6b-walking-m-v0"}
+
+
+def _stage_weights(cfg: zm.TaskCfg, task: str) -> zm.TaskCfg:
     if ":" in task:
         from zbot_lab_amd.envs.walking_v2 import REWARD_CFGS
         cfg.reward_weights = dict(REWARD_CFGS[task.split(":", 1)[1]]["reward_scales"])
+    return cfg
+
+
+def product_cfg(task: str) -> zm.TaskCfg:
+    """The TaskCfg the task's registered env builds (its solver_mode / self_manifold / iterations are
+    read from the env cfg, never restated here: when a default moves, the tests move with it)."""
+    from zbot_lab_amd import tasks
+    return _stage_weights(tasks.load_cfg(ENV_IDS[base_task(task)]).task_cfg(), task)
+
+
+class product:
+    """Context manager: task_cfg() inside returns product_cfg() (solver_mode() / self_manifold() have
+    no effect there), so tolerance_rows and the oracle / sensitivity runs of
+    tests/test_gpu_fullstate.py follow the product configuration unchanged."""
+
+    def __enter__(self):
+        global PRODUCT
+        self.prev, PRODUCT = PRODUCT, True
+
+    def __exit__(self, *exc):
+        global PRODUCT
+        PRODUCT = self.prev
+
+
+def arm_params(values=(None,)):
+    """pytest params (arm, value) of a test with a "pgs" arm (the PGS / self_manifold 2 configuration of
+    task_cfg(), under the ids the test had before it gained the arm) and a "product" arm."""
+    import pytest
+    out = [pytest.param("pgs", v, id="pgs" if v is None else str(v)) for v in values]
+    return out + [pytest.param("product", v, id="product" if v is None else f"product-{v}") for v in values]
+
+
+def arm_context(arm: str):
+    import contextlib
+    return product() if arm == "product" else contextlib.nullcontext()
+
+
+def task_cfg(task: str) -> zm.TaskCfg:
+    if PRODUCT:
+        return product_cfg(task)
+    cfg = {"v2": zm.TaskCfg, "v4": zm.TaskCfg.walking_v4, "standup": zm.TaskCfg.standup,
+           "manager": zm.TaskCfg.manager_flat}[base_task(task)]()
+    _stage_weights(cfg, task)
     cfg.solver_mode = SOLVER_MODE
     if SELF_MANIFOLD is not None:
         cfg.self_manifold = SELF_MANIFOLD

@@ -151,3 +151,25 @@ def test_planted_rare_branch_bugs_are_caught(oracle_lib, task, kind):
     if kind != 5:
         assert listed == set(range(n_plain, n)), listed
     assert stats["deep_draw"] >= len(listed), stats
+
+
+@pytest.mark.parametrize("task", TASKS + ("v2:step0",))
+def test_product_cfg_pins_the_env_defaults(task):
+    """tests/fullstate.product_cfg is the TaskCfg of the task's registered env, and the values it
+    carries today: TGS (solver_mode 1) everywhere, self_manifold 3 for walking v2 and stand-up and 2
+    for v4 and the manager, the reference's 4 position iterations (zbot_cfg.py:637); it differs from
+    the PGS configuration the other parity tests build in exactly those fields; product() routes
+    task_cfg() to it and back."""
+    import dataclasses
+    from fullstate import base_task, product, product_cfg
+    p, t = product_cfg(task), task_cfg(task)
+    four = base_task(task) in ("v2", "standup")
+    assert (p.solver_mode, p.self_manifold) == ((1, 3) if four else (1, 2))
+    assert p.solver_iterations == 4
+    dp, dt = dataclasses.asdict(p), dataclasses.asdict(t)
+    assert dp.keys() == dt.keys()
+    diff = {k for k in dp if dp[k] != dt[k]}
+    assert diff == ({"solver_mode", "self_manifold"} if four else {"solver_mode"}), diff
+    with product():
+        assert dataclasses.asdict(task_cfg(task)) == dp
+    assert dataclasses.asdict(task_cfg(task)) == dt

@@ -22,21 +22,34 @@ from zbot_lab_amd import model as zm
 pytestmark = pytest.mark.gpu
 
 
-def test_c1_four_envs_1000_steps(gpu):
+@pytest.mark.parametrize("arm", ["pgs", "product"])
+def test_c1_four_envs_1000_steps(gpu, monkeypatch, arm):
     """C1 on the HIP path: 4 envs x 1000 random-action steps from a full reset. Every step, the
     oracle is set to the GPU's pre-step state and stepped with the same actions (lock-step), and
     every state row (incl. the 13 per-term episode sums), obs, reward and both flags are compared
     under the full-state rule (tests/test_gpu_fullstate.py: inside tolerance or explained by the
     oracle's own rounding-level sensitivity); the episode log of each step with resets must match.
     The DirectRLEnv bookkeeping invariants hold at every step, and the free-running oracle's episode
-    statistics (4000 samples; chaotic contact lets the trajectories diverge) stay close."""
+    statistics (4000 samples; chaotic contact lets the trajectories diverge) stay close. The product
+    arm builds the three sims from product_cfg("v2") (zb_step_kernel<true,1,false,true>) and runs the
+    comparison and the sensitivity runs inside product()."""
+    from fullstate import arm_context, product_cfg
+    if arm == "product":
+        monkeypatch.delenv("ZB_OCC1", raising=False)
+    with arm_context(arm):
+        _c1(zm.TaskCfg() if arm == "pgs" else product_cfg("v2"), arm == "product")
+
+
+def _c1(cfg, product):
     import torch
     from fullstate import compare
     from oracle.pyoracle import OracleSim
     from zbot_lab_amd.sim import ZbotSim
-    g = ZbotSim(4, zm.TaskCfg(), device="cuda:0", seed=42)
-    o = OracleSim(4, zm.TaskCfg(), seed=42)       # lock-step
-    f = OracleSim(4, zm.TaskCfg(), seed=42)       # free-running
+    g = ZbotSim(4, cfg, device="cuda:0", seed=42)
+    if product:
+        assert g.kernel_variant() == (1, 1, 0, 1)
+    o = OracleSim(4, cfg, seed=42)       # lock-step
+    f = OracleSim(4, cfg, seed=42)       # free-running
     for x in (g, o, f):
         x.reset(None)
     rng = np.random.default_rng(42)

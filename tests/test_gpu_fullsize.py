@@ -18,6 +18,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from fullstate import arm_params
 from helpers import S, perturbed_states
 from zbot_lab_amd import model as zm
 
@@ -45,31 +46,40 @@ def _sample(n, k=1024, seed=0):
     return np.array(sorted(ids), dtype=np.int64)
 
 
-@pytest.mark.parametrize("n", [4096, 8192, 65536])
-def test_full_state_headline_sizes(gpu, n):
+@pytest.mark.parametrize("arm,n", arm_params([4096, 8192, 65536]))
+def test_full_state_headline_sizes(gpu, monkeypatch, arm, n):
     """Walking v2 at BASELINE's sizes (4096 = configs[1], 8192 = one GPU's shard of configs[2],
     65 536 on one GPU): one step of all n envs from random full states (every persistent row: sensor
     histories, timers, feet latches, step lengths, integrators, episode sums), then every state row,
     obs, reward and both flags of a spread sample of 1024 env columns against the oracle run on
     those columns (envs are independent, so the sample is an exact sub-problem), under the
-    full-state rule of tests/test_gpu_fullstate.py: every env inside tolerance or explained."""
+    full-state rule of tests/test_gpu_fullstate.py: every env inside tolerance or explained. The
+    product arm builds the sim and the oracles from product_cfg("v2"): zb_step_kernel<true,1,false,true>
+    at 4096 envs, <true,2,false,true> above."""
     import torch
     import test_gpu_fullstate as F
-    from fullstate import random_states, task_cfg
+    from fullstate import arm_context, random_states, task_cfg
     from oracle.pyoracle import OracleSim
+    from zbot_lab_amd.sim import ZbotSim
     task, seed = "v2", 29
-    st = random_states(task, OracleSim(n, task_cfg(task), seed=seed), n, seed=300 + n)
-    a = np.random.default_rng(n).normal(size=(n, 6)).astype(np.float32)
-    g = _sim(n, seed=seed)
-    g.set_state(torch.from_numpy(st).cuda())
-    obs, rew, te, tr = _step(g, a)
-    sg = g.get_state().cpu().numpy()
-    g.close()
-    ids = _sample(n)
-    sub = lambda x: np.ascontiguousarray(x[:, ids])  # noqa: E731
-    g_out = (np.ascontiguousarray(obs[ids]), rew[ids].copy(), te[ids].copy(), tr[ids].copy())
-    nbad = F._check(task, f"one step of {n} envs, sampled columns", len(ids), seed, sub(st),
-                    [np.ascontiguousarray(a[ids])], g_out, sub(sg), torch)
+    with arm_context(arm):
+        if arm == "product":
+            monkeypatch.delenv("ZB_OCC1", raising=False)
+            g = ZbotSim(n, task_cfg(task), device="cuda:0", seed=seed)
+            assert g.kernel_variant() == (1, 1 if n <= 4096 else 2, 0, 1)
+        else:
+            g = _sim(n, seed=seed)
+        st = random_states(task, OracleSim(n, task_cfg(task), seed=seed), n, seed=300 + n)
+        a = np.random.default_rng(n).normal(size=(n, 6)).astype(np.float32)
+        g.set_state(torch.from_numpy(st).cuda())
+        obs, rew, te, tr = _step(g, a)
+        sg = g.get_state().cpu().numpy()
+        g.close()
+        ids = _sample(n)
+        sub = lambda x: np.ascontiguousarray(x[:, ids])  # noqa: E731
+        g_out = (np.ascontiguousarray(obs[ids]), rew[ids].copy(), te[ids].copy(), tr[ids].copy())
+        label = f"one step of {n} envs, sampled columns" + (" (product cfg)" if arm == "product" else "")
+        nbad = F._check(task, label, len(ids), seed, sub(st), [np.ascontiguousarray(a[ids])], g_out, sub(sg), torch)
     assert nbad <= 0.02 * len(ids)
 
 

@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-from fullstate import TOL, TASKS, compare, perturb_physics, random_states, row_groups, solver_mode, task_cfg
+from fullstate import TOL, TASKS, arm_context, arm_params, compare, perturb_physics, random_states, row_groups, solver_mode, task_cfg
 
 pytestmark = pytest.mark.gpu
 K_SENS = 8
@@ -309,7 +309,7 @@ def _check(task, label, n, seed, st, actions, g_out, sg, torch, wc=None, stats=N
         stats.update(frac=frac, med=med, frac_f32=frac_o, med_f32=med_o, active=int(active.sum()), nbad=len(bad),
                      nbad_f32=nbad_f32)
     _record_stats(task, label, n, frac=frac, med=med, frac_f32=frac_o, med_f32=med_o, frac_vs_f32=frac_g,
-                  med_vs_f32=med_g, active=int(active.sum()), nbad=len(bad), groups=groups)
+                  med_vs_f32=med_g, active=int(active.sum()), nbad=len(bad), nbad_f32=nbad_f32, groups=groups)
     unexplained = [int(e) for e in bad if not _explained(ratio[e], sens[e])]
     ndeep = 0
     if unexplained:
@@ -480,14 +480,22 @@ def test_full_state_tgs(gpu, task, mode):
         assert nbad <= AGG_FRAC_K_MULTI * stats["nbad_f32"] + 0.005 * n, (nbad, stats["nbad_f32"])
 
 
-@pytest.mark.parametrize("task", TASKS)
-def test_full_state_contact_cache(gpu, task):
+@pytest.mark.parametrize("arm,task", arm_params(TASKS))
+def test_full_state_contact_cache(gpu, monkeypatch, arm, task):
     """The persistent self-contact cache (the first substep's GJK warm start):
     from folded states one oracle step after random joint angles (self contacts present) and the
     oracle's cache of those states, set into the GPU handle, one step on both sides; every state row under the
     full-state rule (the oracle run from the same cache), and the cache after the step: pair codes
     identical in >= 99 % of the (slot, env) entries, normals within 2e-3 (95 %) / 5e-2 (99 %) where
-    the codes agree."""
+    the codes agree. The product arm runs the registered env's configuration
+    (tests/fullstate.product_cfg: the TGS kernels, with the ruling-on-face manifold for v2 and stand-up)."""
+    if arm == "product":
+        monkeypatch.delenv("ZB_OCC1", raising=False)
+    with arm_context(arm):
+        _contact_cache(task, arm == "product")
+
+
+def _contact_cache(task, product):
     from oracle.pyoracle import OracleSim
     seed, n = 23, 2048
     o = OracleSim(n, task_cfg(task), seed=seed)
@@ -500,6 +508,8 @@ def test_full_state_contact_cache(gpu, task):
     hot = (wc[3::4] >= 1).any(axis=0)
     assert hot.sum() >= 50, hot.sum()
     g, _, cfg, torch = _sims(task, n, seed)
+    if product:
+        assert g.kernel_variant() == (1, 1, 0, 1 if task in ("v2", "standup") else 0)
     g.set_state(torch.from_numpy(st).cuda())
     g.set_contact_cache(torch.from_numpy(wc).cuda())
     np.testing.assert_array_equal(g.get_contact_cache().cpu().numpy(), wc)

@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from fullstate import arm_params, product_cfg
 from zbot_lab_amd import model as zm
 
 pytestmark = pytest.mark.gpu
@@ -25,13 +26,19 @@ def _penalty(task, cfg):
     return -cfg.terminal_penalty
 
 
-@pytest.mark.parametrize("task", sorted(TASKS))
-def test_non_finite_state_is_reset(gpu, task):
+@pytest.mark.parametrize("arm,task", arm_params(sorted(TASKS)))
+def test_non_finite_state_is_reset(gpu, monkeypatch, arm, task):
+    """The product arm: the registered env's configuration (tests/fullstate.product_cfg), i.e. the
+    guard of the TGS kernels the product launches."""
     import torch
     from zbot_lab_amd.sim import ZbotSim
     n = 256
-    cfg = TASKS[task]()
+    cfg = TASKS[task]() if arm == "pgs" else product_cfg({"walking": "v2"}.get(task, task))
+    if arm == "product":
+        monkeypatch.delenv("ZB_OCC1", raising=False)
     clean, bad = ZbotSim(n, cfg, device="cuda:0", seed=3), ZbotSim(n, cfg, device="cuda:0", seed=3)
+    if arm == "product":
+        assert bad.kernel_variant() == (1, 1, 0, 1 if task in ("walking", "standup") else 0)
     st = clean.get_state().cpu().numpy()
     poisoned = [5, 77, 200]
     st_bad = st.copy()

@@ -40,6 +40,7 @@ def lib():
     L.zb_reset.argtypes = [P, P, C.c_int, P]
     L.zb_step.argtypes = [P, P, P, P, P, P, P]
     L.zb_observe.argtypes = [P, P, P]
+    L.zb_kernel_variant.argtypes = [P, C.POINTER(C.c_int32)]
     L.zb_read_log.argtypes = [P, P, P, P]
     L.zb_set_log_buffers.argtypes = [P, P, P]
     L.zb_set_log_accumulator.argtypes = [P, P]
@@ -67,7 +68,7 @@ def lib():
     L.zb_gjk_pairs.argtypes = [P, P, C.c_int, C.c_float, P, P]
     L.zb_pair_manifold.argtypes = [P, C.c_int, C.c_float, P, P]
     L.zb_pair_manifold_mode.argtypes = [P, C.c_int, C.c_float, C.c_int, P, P]
-    for name in ("zb_create", "zb_num_envs", "zb_reset", "zb_step", "zb_observe", "zb_read_log", "zb_set_log_buffers", "zb_set_log_accumulator", "zb_set_done_buffer",
+    for name in ("zb_create", "zb_num_envs", "zb_reset", "zb_step", "zb_observe", "zb_kernel_variant", "zb_read_log", "zb_set_log_buffers", "zb_set_log_accumulator", "zb_set_done_buffer",
                  "zb_get_state", "zb_set_state", "zb_get_contact_cache", "zb_set_contact_cache", "zb_physics_substeps",
                  "zb_profile_begin", "zb_profile_end", "zb_profile_stride",
                  "zb_state_dim", "zb_set_link_friction", "zb_set_link_friction_sd", "zb_read_curriculum", "zb_gjk_pairs", "zb_pair_manifold", "zb_pair_manifold_mode"):
@@ -76,7 +77,7 @@ def lib():
     return L
 
 
-EXPORTED = ["zb_create", "zb_destroy", "zb_last_error", "zb_num_envs", "zb_reset", "zb_step", "zb_observe",
+EXPORTED = ["zb_create", "zb_destroy", "zb_last_error", "zb_num_envs", "zb_reset", "zb_step", "zb_observe", "zb_kernel_variant",
             "zb_read_log", "zb_set_log_buffers", "zb_set_log_accumulator", "zb_set_done_buffer", "zb_get_state", "zb_set_state", "zb_get_contact_cache",
             "zb_set_contact_cache", "zb_physics_substeps", "zb_profile_begin", "zb_profile_stride",
             "zb_profile_end", "zb_read_stamps", "zb_read_stamps_slowest", "zb_read_stamp_hist", "zb_read_wave_times", "zb_state_dim", "zb_set_link_friction", "zb_set_link_friction_sd",

@@ -5209,6 +5209,21 @@ void zb_launch(F kernel, int blocks, hipStream_t s, hipEvent_t e0, hipEvent_t e1
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WGT), 0, s, args...);
 }
 
+// The step-kernel instantiation of a handle: the template arguments <kTgs, kOcc, kRefresh, kRf> that
+// zb_step's dispatch selects and zb_kernel_variant reports (one place, so the two cannot disagree).
+// Walking v4 and the manager task have <kTgs, kOcc> kernels only (zb_create refuses solver_modes 2, 3
+// and self_manifold 3 there).
+struct StepVariant {
+  bool tgs;
+  int occ;
+  bool refresh, rf;
+};
+
+static StepVariant step_variant(const zb_sim* h) {
+  const bool four = h->task != ZB_TASK_WALKING_V4 && h->task != ZB_TASK_MANAGER_V0;
+  return {h->cfg.solver_mode >= 1, h->occ1 ? 1 : 2, four && h->cfg.solver_mode >= 2, four && h->cfg.self_manifold == 3};
+}
+
 extern "C" {
 
 const char* zb_last_error(void) { return g_err; }
@@ -5578,15 +5593,14 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
   // (the event-recording dispatch adds ~5.7 us to a step: every prof_stride-th launch only)
   const bool prof = h->prof_n < h->prof_max && (h->prof_seen++ % h->prof_stride) == 0;
   hipEvent_t e0 = prof ? h->prof_ev[2 * h->prof_n] : nullptr, e1 = prof ? h->prof_ev[2 * h->prof_n + 1] : nullptr;
-  const bool tgs = h->cfg.solver_mode >= 1, refresh = h->cfg.solver_mode >= 2;
-  const bool one = h->occ1;
+  const StepVariant v = step_variant(h);
+  const bool tgs = v.tgs, refresh = v.refresh, one = v.occ == 1, rf = v.rf;
 #define ZB_LAUNCH(K, ...)                                                                          \
   (tgs ? (one ? zb_launch(K<true, 1>, blocks, s, e0, e1, __VA_ARGS__) : zb_launch(K<true, 2>, blocks, s, e0, e1, __VA_ARGS__)) \
        : (one ? zb_launch(K<false, 1>, blocks, s, e0, e1, __VA_ARGS__) : zb_launch(K<false, 2>, blocks, s, e0, e1, __VA_ARGS__)))
   // solver_modes 2, 3 (the TGS refresh) and self_manifold 3 (the ruling-on-face manifold): walking v2
   // and stand-up only (zb_create); one wave per SIMD at <= 4096 envs as the default kernels (round 6:
   // the refresh's FK and row rebuild inside the sweeps spill at two-wave occupancy)
-  const bool rf = h->cfg.self_manifold == 3;
 #define ZB_LAUNCH_R(K, ...)                                                                        \
   (rf ? (refresh ? (one ? zb_launch(K<true, 1, true, true>, blocks, s, e0, e1, __VA_ARGS__)          \
                         : zb_launch(K<true, 2, true, true>, blocks, s, e0, e1, __VA_ARGS__))         \
@@ -5630,6 +5644,13 @@ int zb_observe(zb_handle h, float* obs, void* stream) {
   else
     zb_observe_kernel<<<(h->n + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->d_model, h->n, h->d_state, obs);
   return launch_check("zb_observe_kernel");
+}
+
+int zb_kernel_variant(zb_handle h, int32_t out[4]) {
+  if (!h || !out) return set_err(-1, "zb_kernel_variant", hipSuccess);
+  const StepVariant v = step_variant(h);
+  out[0] = v.tgs; out[1] = v.occ; out[2] = v.refresh; out[3] = v.rf;
+  return 0;
 }
 
 int zb_state_dim(zb_handle h) { return h ? h->state_dim : -1; }

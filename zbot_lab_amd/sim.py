@@ -99,6 +99,13 @@ class ZbotSim:
         nat.check(self.lib.zb_observe(self._h, nat.ptr(obs), _stream(self.device)), "zb_observe")
         return obs
 
+    def kernel_variant(self) -> tuple:
+        """(kTgs, kOcc, kRefresh, kRf): the template arguments of the step-kernel instantiation the
+        next step() launches (zb_kernel_variant; host only)."""
+        v = (C.c_int32 * 4)()
+        nat.check(self.lib.zb_kernel_variant(self._h, v), "zb_kernel_variant")
+        return tuple(int(x) for x in v)
+
     def read_log(self):
         """(term_means[num_terms], counts[ZB_LOG_COUNTS]) device tensors of the most recent step that had resets
         (registered with zb_set_log_buffers, so no per-step copy)."""
