@@ -40,6 +40,23 @@ typedef struct {
   float* gb[ZBP_MAX_LAYERS];
 } zbp_net;
 
+/* Empirical observation normalization (rsl_rl EmpiricalNormalization; zbot_lab_amd/rl/normalizer.py):
+ * the running statistics of one net's observations, device buffers owned by the caller. Where a net's
+ * input rows are gathered (zbp_minibatch, zbp_act) column k < dim becomes
+ *   (x[k] - mean[k]) / (std[k] + eps)
+ * before the first layer (so the layer-0 weight gradient is the normalized input's); padded columns
+ * stay 0 and the storage-slot copies zbp_act writes stay raw. mean == NULL: identity (a zeroed struct
+ * is exactly the behaviour without it). zbp_norm_update maintains the buffers. */
+typedef struct {
+  float* mean;     /* [dim] running mean (initially 0) */
+  float* var;      /* [dim] running biased variance (initially 1) */
+  float* std;      /* [dim] sqrt(var) (initially 1) */
+  int64_t* count;  /* [1] rows seen so far (initially 0) */
+  float eps;       /* rsl_rl: 1e-2 */
+  int64_t until;   /* the statistics freeze once count >= until; < 0: never */
+  int32_t dim;     /* the net's observation dim (<= 32) */
+} zbp_obs_norm;
+
 /* The rollout (RolloutStorage, flattened [T * N] rows) and this minibatch's rows:
  * rows idx[idx_offset .. idx_offset + batch) of the permutation (int64, rsl_rl's randperm). */
 typedef struct {
@@ -56,6 +73,8 @@ typedef struct {
   int64_t idx_offset;
   int32_t batch;             /* minibatch rows (a multiple of 32) */
   int32_t obs_dim, critic_obs_dim, num_actions;
+  zbp_obs_norm actor_norm;   /* applied to the gathered obs rows (mean == NULL: none) */
+  zbp_obs_norm critic_norm;  /* applied to the gathered critic_obs rows */
 } zbp_batch;
 
 /* PPO loss constants (RslRlPpoAlgorithmCfg) */
@@ -140,6 +159,8 @@ typedef struct {
   int32_t rows, obs_dim, critic_obs_dim, num_actions;
   int32_t noise_step;       /* (noise == NULL) the rollout step: distinct draws per step of a rollout */
   int32_t noise_seed;       /* (noise == NULL) the caller's stream, e.g. one per rank */
+  zbp_obs_norm actor_norm;  /* the actor sees normalized obs (mean == NULL: none); st_obs stays raw */
+  zbp_obs_norm critic_norm; /* the critic sees normalized critic_obs; st_critic_obs stays raw */
 } zbp_act_io;
 int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param, const zbp_act_io* io, float* ws,
             int32_t batch, void* stream);
@@ -151,6 +172,20 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
 int zbp_env_post(const float* rewards, const int64_t* dones, const uint8_t* time_outs, const float* values, float gamma,
                  float* st_rewards, float* st_dones, float* cur_rew, float* cur_len, float* ep_stats, int32_t n,
                  void* stream);
+/* EmpiricalNormalization.update for one batch of `rows` >= 1 observations ([rows][dim], contiguous),
+ * entirely on the device (no host sync: capturable between the env step and the next zbp_act). Per
+ * normalizer, unless until >= 0 and count >= until:
+ *   count += rows; rate = rows / count; delta = mean_x - mean; mean += rate * delta;
+ *   var += rate * (var_x - var + delta * (mean_x - mean_new)); std = sqrt(var)
+ * with mean_x / var_x the column mean and biased variance of the batch. Two launches: per-workgroup
+ * two-pass partials (mean, sum of squared deviations) over fixed row ranges, then one workgroup per
+ * normalizer that combines them around the batch mean in a fixed order and merges into the running
+ * statistics -- fp64 inside, no atomics, bit-identical from run to run. Either normalizer may be NULL
+ * (or have mean == NULL); with both and obs == critic_obs (same pointer and dim) the batch is read
+ * once. scratch: zbp_norm_scratch_floats(rows) floats, 8-byte aligned, private to the call's stream. */
+int64_t zbp_norm_scratch_floats(int32_t rows);
+int zbp_norm_update(const zbp_obs_norm* actor, const zbp_obs_norm* critic, const float* obs, const float* critic_obs,
+                    int32_t rows, float* scratch, void* stream);
 const char* zbp_last_error(void);
 
 #ifdef __cplusplus

@@ -5,7 +5,9 @@ Sequence (play.py:85-200): resolve the checkpoint (``--checkpoint <file>``, else
 ``get_checkpoint_path(logs/rsl_rl/<experiment>, --load_run, load_checkpoint)``), build the env and
 ``RslRlVecEnvWrapper``, ``OnPolicyRunner(..., log_dir=None)``, ``runner.load``,
 ``runner.get_inference_policy``, export the actor to ``<run>/exported/policy.pt`` with
-``export_policy_as_jit`` (ONNX needs the absent ``onnx`` package), then roll the policy out under
+``export_policy_as_jit`` (ONNX needs the absent ``onnx`` package; a policy trained with
+``actor_obs_normalization`` exports ``actor(normalizer(obs))``, the normalizer picked off the policy
+as play.py:165 does), then roll the policy out under
 ``torch.inference_mode``. There is no viewer, so the loop runs ``--num_steps`` steps and prints one
 JSON summary: mean reward per step, finished episodes (length, return, termination split) and the
 gait: the root's mean forward (+x, the heading the v2 rewards hold, v2.py:320-327) velocity and the
@@ -97,7 +99,9 @@ def main(argv=None) -> dict:
     policy = runner.get_inference_policy(device=env.unwrapped.device)
     exported = None
     if not args.no_export:
-        exported = export_policy_as_jit(runner.alg.policy, normalizer=None,
+        normalizer = runner.alg.policy.actor_obs_normalizer
+        exported = export_policy_as_jit(runner.alg.policy,
+                                        normalizer=None if isinstance(normalizer, torch.nn.Identity) else normalizer,
                                         path=os.path.join(os.path.dirname(resume_path), "exported"),
                                         filename="policy.pt")
 

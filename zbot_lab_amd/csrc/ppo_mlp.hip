@@ -19,7 +19,9 @@
 //
 // and, on one GPU, k_adam (adaptive learning rate, global-norm clipping from k_reduce's per-tile sums
 // of squares, or k_norm's, Adam) + the re-pack (k_pack, which also writes the new rate and step); the rollout's policy step (k_act_reg / k_act), its bookkeeping (k_env_post) and
-// GAE (k_gae, k_adv_stats, k_adv_norm). Exact fp32 throughout (the MFMA is a k-ordered fmaf chain);
+// GAE (k_gae, k_adv_stats, k_adv_norm). Empirical observation normalization (zbp_obs_norm) is applied
+// where a row tile's inputs are gathered, and its running statistics are kept by k_obs_part /
+// k_obs_merge (zbp_norm_update). Exact fp32 throughout (the MFMA is a k-ordered fmaf chain);
 // results differ from torch's only by summation order. MI355X mapping: the weights (<= 450 KB per
 // net) stay L2-resident; design and measurements in DESIGN.md §7 (round 5).
 #include <hip/hip_runtime.h>
@@ -180,6 +182,14 @@ const char* check_net(const zbp_net* n) {
   if (n->dim[n->n_layers] < 1 || n->dim[n->n_layers] > 32) return "output dim must be 1..32";
   for (int l = 0; l < n->n_layers; ++l)
     if (!n->w[l] || !n->b[l]) return "null weight / bias";
+  return nullptr;
+}
+
+// an observation normalizer in use (mean != NULL) has every buffer and the net's input dim
+const char* check_norm(const zbp_obs_norm* n, int dim) {
+  if (!n || !n->mean) return nullptr;
+  if (!n->var || !n->std || !n->count) return "obs normalizer: null var / std / count";
+  if (n->dim != dim || dim < 1 || dim > 32) return "obs normalizer: dim must be the net's observation dim";
   return nullptr;
 }
 
@@ -368,13 +378,22 @@ __device__ void net_backward(const RowArgs& A, const NetW& w, float* lds, int ro
   }
 }
 
-// gather the tile's input rows (obs or critic obs) into X_0 (LDS + HBM), zero-padded
-__device__ void gather_input(const RowArgs& A, const NetW& w, const float* src, int dim, float* lds, int row0) {
+// EmpiricalNormalization.forward on column k < dim of a gathered input row (zbp_obs_norm; a division,
+// as torch's (x - mean) / (std + eps))
+__device__ __forceinline__ float obs_normalize(const zbp_obs_norm& nr, int k, float v) {
+  return (v - nr.mean[k]) / (nr.std[k] + nr.eps);
+}
+
+// gather the tile's input rows (obs or critic obs) into X_0 (LDS + HBM), zero-padded; normalized
+// when the net has a normalizer (nr.mean != NULL)
+__device__ void gather_input(const RowArgs& A, const NetW& w, const float* src, int dim, const zbp_obs_norm& nr,
+                             float* lds, int row0) {
   const int P0 = w.p[0];
   for (int e = threadIdx.x; e < TR * P0; e += blockDim.x) {
     const int k = e / TR, i = e % TR;
     const int64_t row = A.bt.idx[A.bt.idx_offset + row0 + i];
-    const float v = k < dim ? src[row * dim + k] : 0.f;
+    float v = k < dim ? src[row * dim + k] : 0.f;
+    if (nr.mean && k < dim) v = obs_normalize(nr, k, v);
     lds[A.lds_x[0] + i * (P0 + 4) + k] = v;
     A.ws[w.x[0] + rbo(P0, k, row0 + i)] = v;
   }
@@ -398,7 +417,7 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
 
   // ---- actor: forward, Gaussian log-prob, clipped surrogate, KL; dL/dmu into dZ of the output
   const NetW& wa = A.n[0];
-  gather_input(A, wa, bt.obs, bt.obs_dim, lds, row0);
+  gather_input(A, wa, bt.obs, bt.obs_dim, bt.actor_norm, lds, row0);
   net_forward(A, wa, lds, row0);
   {
     float* dz = lds + A.lds_dz;
@@ -460,7 +479,7 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
 
   // ---- critic: forward, clipped value loss, backward
   const NetW& wc = A.n[1];
-  gather_input(A, wc, bt.critic_obs, bt.critic_obs_dim, lds, row0);
+  gather_input(A, wc, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, lds, row0);
   net_forward(A, wc, lds, row0);
   {
     float* dz = lds + A.lds_dz;
@@ -648,8 +667,11 @@ __device__ __forceinline__ void rr_backward(const NetW& w, int l, float* __restr
 }
 
 // the tile's input rows (through the permutation) as the first layer's B operand, zero-padded to 32
+// (kNorm: normalized when the net has a normalizer; the register kernels are instantiated without it
+// for nets that have none, so those keep their code and register budget)
+template <bool kNorm>
 __device__ __forceinline__ void rr_gather(const NetW& w, float* __restrict__ ws, int row0, const float* src, int dim,
-                                          int64_t row, Tile (&x)[2]) {
+                                          const zbp_obs_norm& nr, int64_t row, Tile (&x)[2]) {
   const int lo = rr_lane_off(32);
   float* xb = rr_base(ws + w.x[0], 32, row0);
   const float* sr = src + row * dim;
@@ -658,7 +680,8 @@ __device__ __forceinline__ void rr_gather(const NetW& w, float* __restrict__ ws,
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int k = 16 * o + 4 * rr_g() + u;
-      const float v = k < dim ? sr[k] : 0.f;
+      float v = k < dim ? sr[k] : 0.f;
+      if (kNorm && nr.mean && k < dim) v = obs_normalize(nr, k, v);
       x[o][u] = v;
       rr_at(xb, o, u)[lo] = v;
     }
@@ -686,7 +709,7 @@ __device__ __forceinline__ float rr_feat_sum(float v) {
 }
 
 constexpr int RR_TR = 16;  // rows per wave
-template <int T1, int T2, int T3>
+template <int T1, int T2, int T3, bool kNorm>
 __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   constexpr int CB = rr_cb<T1>();
   __shared__ float4 wl[2 * CB * 64];
@@ -725,7 +748,7 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   rr_fetch<2 * T1, CB>(ws + wa.wr[0], 0, wst);
   {
     Tile x0[2], x1[T1], x2[T2], x3[T3];
-    rr_gather(wa, ws, row0, bt.obs, bt.obs_dim, row, x0);
+    rr_gather<kNorm>(wa, ws, row0, bt.obs, bt.obs_dim, bt.actor_norm, row, x0);
     rr_forward<2, T1, false, true, T1 * T2, CB>(wa, 0, ws, wl, row0, x0, x1, wst, ws + wa.wr[1]);
     rr_forward<T1, T2, false, true, T2 * T3, CB>(wa, 1, ws, wl, row0, x1, x2, wst, ws + wa.wr[2]);
     rr_forward<T2, T3, false, true, T3 * 2, CB>(wa, 2, ws, wl, row0, x2, x3, wst, ws + wa.wr[3]);
@@ -793,7 +816,7 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   rr_fetch<2 * T1, CB>(ws + wc.wr[0], 0, wst);
   {
     Tile x0[2], x1[T1], x2[T2], x3[T3];
-    rr_gather(wc, ws, row0, bt.critic_obs, bt.critic_obs_dim, row, x0);
+    rr_gather<kNorm>(wc, ws, row0, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, row, x0);
     rr_forward<2, T1, false, true, T1 * T2, CB>(wc, 0, ws, wl, row0, x0, x1, wst, ws + wc.wr[1]);
     rr_forward<T1, T2, false, true, T2 * T3, CB>(wc, 1, ws, wl, row0, x1, x2, wst, ws + wc.wr[2]);
     rr_forward<T2, T3, false, true, T3 * 2, CB>(wc, 2, ws, wl, row0, x2, x3, wst, ws + wc.wr[3]);
@@ -1173,6 +1196,7 @@ struct ActArgs {
   int obs_dim, cobs_dim, na, rows;
   float *actions, *s_obs, *s_cobs, *s_act, *s_val, *s_lp, *s_mu, *s_sig;
   int lds_x[MAXL], lds_out;
+  zbp_obs_norm nrm[2];  // the actor's / critic's observation normalizer (mean == nullptr: none)
 };
 // The in-kernel action noise (zbp_act with io->noise == NULL): a standard normal per (row, action)
 // from a counter-based draw -- splitmix64 of (the caller's seed, e.g. per rank; the workspace's draw
@@ -1194,22 +1218,24 @@ __device__ __forceinline__ float noise_at(const ActArgs& A, int row, int n) {
   return sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
-__device__ void act_gather(const NetW& w, const float* src, int dim, float* st, int rows, float* lds, int lds_x0,
-                           int row0) {
+// (the storage slot gets the raw observation, the net the normalized one)
+__device__ void act_gather(const NetW& w, const float* src, int dim, const zbp_obs_norm& nr, float* st, int rows,
+                           float* lds, int lds_x0, int row0) {
   const int P0 = w.p[0];
   for (int e = threadIdx.x; e < TR * P0; e += blockDim.x) {
     const int i = e / P0, k = e % P0;  // (row-major: the source rows are contiguous)
     const int row = row0 + i;
-    const float v = (k < dim && row < rows) ? src[(int64_t)row * dim + k] : 0.f;
-    lds[lds_x0 + i * (P0 + 4) + k] = v;
-    if (k < dim && row < rows) st[(int64_t)row * dim + k] = v;
+    const bool in = k < dim && row < rows;
+    const float v = in ? src[(int64_t)row * dim + k] : 0.f;
+    lds[lds_x0 + i * (P0 + 4) + k] = (in && nr.mean) ? obs_normalize(nr, k, v) : v;
+    if (in) st[(int64_t)row * dim + k] = v;
   }
   __syncthreads();
 }
 __global__ __launch_bounds__(256) void k_act(ActArgs A) {
   extern __shared__ float lds[];
   const int row0 = blockIdx.x * TR, tid = threadIdx.x;
-  act_gather(A.n[0], A.obs, A.obs_dim, A.s_obs, A.rows, lds, A.lds_x[0], row0);
+  act_gather(A.n[0], A.obs, A.obs_dim, A.nrm[0], A.s_obs, A.rows, lds, A.lds_x[0], row0);
   net_forward_t<false>(A.n[0], A.ws, 0, A.lds_x, A.lds_out, lds, row0);
   if (tid < TR && row0 + tid < A.rows) {
     const int64_t row = row0 + tid;
@@ -1227,14 +1253,14 @@ __global__ __launch_bounds__(256) void k_act(ActArgs A) {
     A.s_lp[row] = lp;
   }
   __syncthreads();  // (the output tile is reused by the critic)
-  act_gather(A.n[1], A.cobs, A.cobs_dim, A.s_cobs, A.rows, lds, A.lds_x[0], row0);
+  act_gather(A.n[1], A.cobs, A.cobs_dim, A.nrm[1], A.s_cobs, A.rows, lds, A.lds_x[0], row0);
   net_forward_t<false>(A.n[1], A.ws, 0, A.lds_x, A.lds_out, lds, row0);
   if (tid < TR && row0 + tid < A.rows) A.s_val[row0 + tid] = lds[A.lds_out + tid * 33];
 }
 
 // k_act on the register-resident forward (k_rows_reg's shapes): one wave per 16 rows, the weights
 // shared through LDS
-template <int T1, int T2, int T3>
+template <int T1, int T2, int T3, bool kNorm>
 #ifndef ZBP_ACT_REG_MIN
 #define ZBP_ACT_REG_MIN 4096
 #endif
@@ -1264,7 +1290,7 @@ __global__ __launch_bounds__(RR_WG, 2) void k_act_reg(ActArgs A) {
     for (int j = 0; j < 8; ++j) {
       const int k = 16 * (j >> 2) + 4 * gq + (j & 3);
       const float v = (ok && k < dim) ? src[k] : 0.f;
-      x0[j >> 2][j & 3] = v;
+      x0[j >> 2][j & 3] = (kNorm && A.nrm[net].mean && ok && k < dim) ? obs_normalize(A.nrm[net], k, v) : v;
       if (ok && k < dim) st[k] = v;
     }
     rr_forward<2, T1, false, false, T1 * T2, CB>(w, 0, A.ws, wl, 0, x0, x1, wst, A.ws + w.wr[1]);
@@ -1346,7 +1372,7 @@ __device__ __forceinline__ void as_layer(const float* __restrict__ img, const fl
   for (int o = 0; o < TO; ++o) out[o] = xs[o * 64 + lane];
 }
 
-template <int T1, int T2, int T3>
+template <int T1, int T2, int T3, bool kNorm>
 __global__ __launch_bounds__(256, 2) void k_act_split(ActArgs A) {
   static_assert(T1 % 4 == 0 && T2 % 4 == 0 && T3 % 4 == 0, "output tiles split over four waves");
   constexpr int TM = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
@@ -1366,7 +1392,7 @@ __global__ __launch_bounds__(256, 2) void k_act_split(ActArgs A) {
     for (int j = 0; j < 8; ++j) {
       const int k = 16 * (j >> 2) + 4 * gq + (j & 3);
       const float v = (ok && k < dim) ? src[k] : 0.f;
-      x0[j >> 2][j & 3] = v;
+      x0[j >> 2][j & 3] = (kNorm && A.nrm[net].mean && ok && k < dim) ? obs_normalize(A.nrm[net], k, v) : v;
       if (wv == 0 && ok && k < dim) st[k] = v;
     }
   }
@@ -1542,6 +1568,103 @@ __global__ __launch_bounds__(256) void k_adv_norm(float* __restrict__ adv, int64
     adv[e] = (adv[e] - mean) / den;  // (a division, as torch's (adv - mean) / (std + 1e-8))
 }
 
+// ------------------------------------------------------------------------------- observation statistics
+// EmpiricalNormalization.update (zbot_lab_amd/rl/normalizer.py) for one batch of rows, in two launches
+// with the kernel boundary as the only ordering (no grid-wide fence, no atomics):
+//   k_obs_part   workgroup b of G takes the fixed row range [b rows / G, (b + 1) rows / G) of a source
+//                 and computes per column, in two passes, the range's mean and its sum of squared
+//                 deviations from that mean (the range is a few KB: the second pass hits L1 / L2)
+//   k_obs_merge  one workgroup per normalizer: the batch mean from the partial means, then the batch's
+//                 sum of squared deviations around it (sum_b M2_b + n_b (mean_b - mean)^2: a two-pass
+//                 over the partials, no E[x^2] - E[x]^2 anywhere), then count, the `until` test and the
+//                 merge into the running statistics
+// Every sum runs in a fixed order over fixed ranges, so the result does not depend on the workgroup
+// schedule. The arithmetic is fp64 (a few thousand adds per launch); the state stays fp32 / int64.
+constexpr int NORM_MAX_PARTS = 256;  // workgroups of k_obs_part per source
+constexpr int NORM_PART_ROWS = 64;   // rows per workgroup up to NORM_MAX_PARTS * 64 rows, more beyond
+inline int norm_parts(int rows) {
+  const int g = (rows + NORM_PART_ROWS - 1) / NORM_PART_ROWS;
+  return g < NORM_MAX_PARTS ? g : NORM_MAX_PARTS;
+}
+struct NormArgs {
+  zbp_obs_norm nrm[2];  // targets (mean == nullptr: none)
+  int src[2];           // the source each target reads
+  const float* x[2];    // sources [rows][dim[s]]
+  int dim[2];
+  int rows, G;
+  double* part;  // [source][G][2][32]: column means, sums of squared deviations
+};
+__device__ __forceinline__ int norm_row0(int b, int rows, int G) { return (int)((int64_t)b * rows / G); }
+
+__global__ __launch_bounds__(256) void k_obs_part(NormArgs A) {
+  __shared__ double red[2][8][32];
+  const int s = blockIdx.y, b = blockIdx.x, c = threadIdx.x & 31, j = threadIdx.x >> 5;
+  const int D = A.dim[s], r0 = norm_row0(b, A.rows, A.G), r1 = norm_row0(b + 1, A.rows, A.G);
+  const float* x = A.x[s];
+  double sum = 0.0;
+  if (c < D)
+    for (int r = r0 + j; r < r1; r += 8) sum += (double)x[(int64_t)r * D + c];
+  red[0][j][c] = sum;
+  __syncthreads();
+  double mean = 0.0;
+  for (int k = 0; k < 8; ++k) mean += red[0][k][c];
+  mean /= (double)(r1 - r0);
+  double q = 0.0;
+  if (c < D)
+    for (int r = r0 + j; r < r1; r += 8) {
+      const double d = (double)x[(int64_t)r * D + c] - mean;
+      q += d * d;
+    }
+  red[1][j][c] = q;
+  __syncthreads();
+  if (j == 0) {
+    double m2 = 0.0;
+    for (int k = 0; k < 8; ++k) m2 += red[1][k][c];
+    double* p = A.part + ((int64_t)s * A.G + b) * 64;
+    p[c] = mean;
+    p[32 + c] = m2;
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_obs_merge(NormArgs A) {
+  __shared__ double red[32][32];
+  const zbp_obs_norm& nr = A.nrm[blockIdx.x];
+  if (!nr.mean) return;
+  const int64_t count0 = *nr.count;
+  if (nr.until >= 0 && count0 >= nr.until) return;  // (uniform: every thread reads the same count)
+  const int c = threadIdx.x & 31, j = threadIdx.x >> 5, G = A.G, rows = A.rows;
+  const double* part = A.part + (int64_t)A.src[blockIdx.x] * G * 64;
+  double acc = 0.0;
+  for (int b = j; b < G; b += 32) acc += (double)(norm_row0(b + 1, rows, G) - norm_row0(b, rows, G)) * part[b * 64 + c];
+  red[j][c] = acc;
+  __syncthreads();
+  double mean_x = 0.0;
+  for (int k = 0; k < 32; ++k) mean_x += red[k][c];
+  mean_x /= (double)rows;
+  __syncthreads();
+  acc = 0.0;
+  for (int b = j; b < G; b += 32) {
+    const double d = part[b * 64 + c] - mean_x;
+    acc += part[b * 64 + 32 + c] + (double)(norm_row0(b + 1, rows, G) - norm_row0(b, rows, G)) * d * d;
+  }
+  red[j][c] = acc;
+  __syncthreads();
+  if (j == 0 && c < nr.dim) {
+    double m2 = 0.0;
+    for (int k = 0; k < 32; ++k) m2 += red[k][c];
+    const double var_x = m2 / (double)rows;
+    const double rate = (double)rows / (double)(count0 + rows);
+    const double mean0 = (double)nr.mean[c], var0 = (double)nr.var[c];
+    const double delta = mean_x - mean0, mean1 = mean0 + rate * delta;
+    const float var1 = (float)(var0 + rate * (var_x - var0 + delta * (mean_x - mean1)));
+    nr.mean[c] = (float)mean1;
+    nr.var[c] = var1;
+    nr.std[c] = sqrtf(var1);
+  }
+  __syncthreads();  // (every thread has read the old count)
+  if (threadIdx.x == 0) *nr.count = count0 + rows;
+}
+
 // k_rows_reg instantiation for the nets' shape: 1 = hidden [256, 256, 128], 2 = [128, 128, 128] (both
 // nets; inputs / outputs <= 32), 0 = none (k_rows)
 int reg_shape(const Layout& lo, int B = 128) {
@@ -1620,6 +1743,8 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
     return fail(-1, "zbp_minibatch: num_actions must match the actor output (<= 13)");
   if (batch->obs_dim != actor->dim[0] || batch->critic_obs_dim != critic->dim[0] || critic->dim[critic->n_layers] != 1)
     return fail(-1, "zbp_minibatch: observation dims / critic output");
+  if (const char* e = check_norm(&batch->actor_norm, batch->obs_dim)) return fail(-1, e);
+  if (const char* e = check_norm(&batch->critic_norm, batch->critic_obs_dim)) return fail(-1, e);
   for (int k = 0; k < 2; ++k) {
     const zbp_net* n = k ? critic : actor;
     for (int l = 0; l < n->n_layers; ++l)
@@ -1659,10 +1784,15 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   }
   // the register-resident row kernel for the shipped shapes (ZBP_ROWS=lds: the LDS one, for A/Bs)
   const int shape = reg_shape(lo, B);
-  if (shape == 1)
-    k_rows_reg<16, 16, 8><<<2 * (B / 64), RR_WG, 0, s>>>(R);
+  const bool norm = batch->actor_norm.mean || batch->critic_norm.mean;
+  if (shape == 1 && norm)
+    k_rows_reg<16, 16, 8, true><<<2 * (B / 64), RR_WG, 0, s>>>(R);
+  else if (shape == 1)
+    k_rows_reg<16, 16, 8, false><<<2 * (B / 64), RR_WG, 0, s>>>(R);
+  else if (shape == 2 && norm)
+    k_rows_reg<8, 8, 8, true><<<2 * (B / 64), RR_WG, 0, s>>>(R);
   else if (shape == 2)
-    k_rows_reg<8, 8, 8><<<2 * (B / 64), RR_WG, 0, s>>>(R);
+    k_rows_reg<8, 8, 8, false><<<2 * (B / 64), RR_WG, 0, s>>>(R);
   else
     k_rows<<<B / TR, ROW_THREADS, lds, s>>>(R);
   if (int rc = launch_check("k_rows")) return rc;
@@ -1765,6 +1895,8 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
   if (io->num_actions != actor->dim[actor->n_layers] || io->obs_dim != actor->dim[0] ||
       io->critic_obs_dim != critic->dim[0] || critic->dim[critic->n_layers] != 1)
     return fail(-1, "zbp_act: observation / action dims");
+  if (const char* e = check_norm(&io->actor_norm, io->obs_dim)) return fail(-1, e);
+  if (const char* e = check_norm(&io->critic_norm, io->critic_obs_dim)) return fail(-1, e);
   const Layout lo = make_layout(actor, critic, batch);
   ActArgs A{};
   A.n[0] = lo.n[0];
@@ -1789,6 +1921,8 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
   A.s_lp = io->st_log_prob;
   A.s_mu = io->st_mu;
   A.s_sig = io->st_sigma;
+  A.nrm[0] = io->actor_norm;
+  A.nrm[1] = io->critic_norm;
   int off = 0;
   for (int l = 0; l < MAXL; ++l) {
     const int p = lo.n[0].p[l] > lo.n[1].p[l] ? lo.n[0].p[l] : lo.n[1].p[l];
@@ -1815,14 +1949,22 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
   // the 128-wide nets (shape 2): the split-output forward (k_act_split, round 6) up to
   // ZBP_ACT_SPLIT_MAX rows; ZBP_ACT=reg / lds / split forces a kernel for A/Bs and tests
   const bool split = shape == 2 && !f_reg && (f_split || io->rows <= ZBP_ACT_SPLIT_MAX);
-  if (split)
-    k_act_split<8, 8, 8><<<2 * ((io->rows + 15) / 16), 256, 0, (hipStream_t)stream>>>(A);
+  const bool norm = A.nrm[0].mean || A.nrm[1].mean;
+  hipStream_t s = (hipStream_t)stream;
+  if (split && norm)
+    k_act_split<8, 8, 8, true><<<2 * ((io->rows + 15) / 16), 256, 0, s>>>(A);
+  else if (split)
+    k_act_split<8, 8, 8, false><<<2 * ((io->rows + 15) / 16), 256, 0, s>>>(A);
+  else if (shape == 1 && norm)
+    k_act_reg<16, 16, 8, true><<<wgs, RR_WG, 0, s>>>(A);
   else if (shape == 1)
-    k_act_reg<16, 16, 8><<<wgs, RR_WG, 0, (hipStream_t)stream>>>(A);
+    k_act_reg<16, 16, 8, false><<<wgs, RR_WG, 0, s>>>(A);
+  else if (shape == 2 && norm)
+    k_act_reg<8, 8, 8, true><<<wgs, RR_WG, 0, s>>>(A);
   else if (shape == 2)
-    k_act_reg<8, 8, 8><<<wgs, RR_WG, 0, (hipStream_t)stream>>>(A);
+    k_act_reg<8, 8, 8, false><<<wgs, RR_WG, 0, s>>>(A);
   else
-    k_act<<<(io->rows + TR - 1) / TR, 256, lds, (hipStream_t)stream>>>(A);
+    k_act<<<(io->rows + TR - 1) / TR, 256, lds, s>>>(A);
   return launch_check("k_act");
 }
 
@@ -1834,6 +1976,43 @@ int zbp_env_post(const float* rewards, const int64_t* dones, const uint8_t* time
   k_env_post<<<1, 1024, 0, (hipStream_t)stream>>>(rewards, dones, time_outs, values, gamma, st_rewards, st_dones, cur_rew,
                                                   cur_len, ep_stats, n);
   return launch_check("k_env_post");
+}
+
+int64_t zbp_norm_scratch_floats(int32_t rows) {
+  if (rows < 1) return -1;
+  return (int64_t)2 * norm_parts(rows) * 64 * (int64_t)(sizeof(double) / sizeof(float));
+}
+
+int zbp_norm_update(const zbp_obs_norm* actor, const zbp_obs_norm* critic, const float* obs, const float* critic_obs,
+                    int32_t rows, float* scratch, void* stream) {
+  const zbp_obs_norm* nr[2] = {actor && actor->mean ? actor : nullptr, critic && critic->mean ? critic : nullptr};
+  const float* x[2] = {obs, critic_obs};
+  if (!nr[0] && !nr[1]) return 0;
+  if (rows < 1 || !scratch || ((uintptr_t)scratch & 7)) return fail(-1, "zbp_norm_update: rows / scratch");
+  NormArgs A{};
+  int nsrc = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (!nr[k]) continue;
+    if (const char* e = check_norm(nr[k], nr[k]->dim)) return fail(-1, e);
+    if (!x[k]) return fail(-1, "zbp_norm_update: null observations");
+    A.nrm[k] = *nr[k];
+    // both normalizers on the same rows (every task here: obs == critic_obs): one read serves both
+    if (k == 1 && nsrc == 1 && x[1] == A.x[0] && nr[1]->dim == A.dim[0]) {
+      A.src[1] = 0;
+      continue;
+    }
+    A.src[k] = nsrc;
+    A.x[nsrc] = x[k];
+    A.dim[nsrc++] = nr[k]->dim;
+  }
+  A.rows = rows;
+  A.G = norm_parts(rows);
+  A.part = reinterpret_cast<double*>(scratch);
+  hipStream_t s = (hipStream_t)stream;
+  k_obs_part<<<dim3(A.G, nsrc), 256, 0, s>>>(A);
+  if (int rc = launch_check("k_obs_part")) return rc;
+  k_obs_merge<<<2, 1024, 0, s>>>(A);
+  return launch_check("k_obs_merge");
 }
 
 int zbp_gae(const float* rewards, const float* dones, const float* values, const float* last_values, float* returns,

@@ -31,11 +31,18 @@ class Net(C.Structure):
                 ("b", C.c_void_p * MAXL), ("gw", C.c_void_p * MAXL), ("gb", C.c_void_p * MAXL)]
 
 
+class ObsNorm(C.Structure):
+    """zbp_obs_norm: one EmpiricalNormalization's device buffers (all zero: identity)."""
+    _fields_ = [("mean", C.c_void_p), ("var", C.c_void_p), ("std", C.c_void_p), ("count", C.c_void_p),
+                ("eps", C.c_float), ("until", C.c_int64), ("dim", C.c_int32)]
+
+
 class Batch(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("critic_obs", C.c_void_p), ("actions", C.c_void_p), ("values", C.c_void_p),
                 ("advantages", C.c_void_p), ("returns", C.c_void_p), ("log_prob", C.c_void_p), ("mu", C.c_void_p),
                 ("sigma", C.c_void_p), ("idx", C.c_void_p), ("idx_offset", C.c_int64), ("batch", C.c_int32),
-                ("obs_dim", C.c_int32), ("critic_obs_dim", C.c_int32), ("num_actions", C.c_int32)]
+                ("obs_dim", C.c_int32), ("critic_obs_dim", C.c_int32), ("num_actions", C.c_int32),
+                ("actor_norm", ObsNorm), ("critic_norm", ObsNorm)]
 
 
 class LossCfg(C.Structure):
@@ -48,7 +55,7 @@ class ActIO(C.Structure):
                 ("st_obs", C.c_void_p), ("st_critic_obs", C.c_void_p), ("st_actions", C.c_void_p),
                 ("st_values", C.c_void_p), ("st_log_prob", C.c_void_p), ("st_mu", C.c_void_p), ("st_sigma", C.c_void_p),
                 ("rows", C.c_int32), ("obs_dim", C.c_int32), ("critic_obs_dim", C.c_int32), ("num_actions", C.c_int32),
-                ("noise_step", C.c_int32), ("noise_seed", C.c_int32)]
+                ("noise_step", C.c_int32), ("noise_seed", C.c_int32), ("actor_norm", ObsNorm), ("critic_norm", ObsNorm)]
 
 
 class Params(C.Structure):
@@ -58,7 +65,7 @@ class Params(C.Structure):
 
 
 EXPORTED = ["zbp_workspace_floats", "zbp_pack", "zbp_minibatch", "zbp_optimizer_step", "zbp_gae", "zbp_act",
-            "zbp_env_post", "zbp_last_error"]
+            "zbp_env_post", "zbp_norm_scratch_floats", "zbp_norm_update", "zbp_last_error"]
 _lib = None
 
 
@@ -98,7 +105,11 @@ def lib():
     L.zbp_gae.argtypes = [P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, P, P]
     L.zbp_act.argtypes = [C.POINTER(Net), C.POINTER(Net), P, C.POINTER(ActIO), P, C.c_int32, P]
     L.zbp_env_post.argtypes = [P, P, P, P, C.c_float, P, P, P, P, P, C.c_int32, P]
-    for n in ("zbp_pack", "zbp_minibatch", "zbp_optimizer_step", "zbp_gae", "zbp_act", "zbp_env_post"):
+    L.zbp_norm_scratch_floats.restype = C.c_int64
+    L.zbp_norm_scratch_floats.argtypes = [C.c_int32]
+    L.zbp_norm_update.argtypes = [C.POINTER(ObsNorm), C.POINTER(ObsNorm), P, P, C.c_int32, P, P]
+    for n in ("zbp_pack", "zbp_minibatch", "zbp_optimizer_step", "zbp_gae", "zbp_act", "zbp_env_post",
+              "zbp_norm_update"):
         getattr(L, n).restype = C.c_int
     _lib = L
     return L
@@ -176,6 +187,22 @@ def _net(layers) -> Net:
     return n
 
 
+def obs_norm(module) -> ObsNorm:
+    """zbp_obs_norm of an ActorCritic's normalizer submodule: the buffers of an
+    ``EmpiricalNormalization``, or all zero (identity) for ``nn.Identity``."""
+    n = ObsNorm()
+    if isinstance(module, nn.Identity):
+        return n
+    for t, dt in ((module._mean, torch.float32), (module._var, torch.float32), (module._std, torch.float32),
+                  (module.count, torch.int64)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ZbotError("observation normalizer buffers must be contiguous fp32 / int64 GPU tensors")
+    n.mean, n.var, n.std = module._mean.data_ptr(), module._var.data_ptr(), module._std.data_ptr()
+    n.count = module.count.data_ptr()
+    n.eps, n.until, n.dim = float(module.eps), -1 if module.until is None else int(module.until), module._mean.shape[-1]
+    return n
+
+
 class FusedUpdate:
     """The PPO update's minibatches on libzbot_ppo (one GPU: the optimizer too)."""
 
@@ -193,6 +220,8 @@ class FusedUpdate:
     def _bind(self) -> None:
         """(Re)read every pointer: parameters, .grad buffers, workspace (after a checkpoint load)."""
         self.na, self.nc = _net(self.la), _net(self.lc)
+        pol = self.alg.policy
+        self.norm_a, self.norm_c = obs_norm(pol.actor_obs_normalizer), obs_norm(pol.critic_obs_normalizer)
         n = lib().zbp_workspace_floats(C.byref(self.na), C.byref(self.nc), self.batch)
         if n < 0:
             raise ZbotError("zbp_workspace_floats: unsupported shapes")
@@ -217,6 +246,7 @@ class FusedUpdate:
         b.mu, b.sigma = storage.mu.data_ptr(), storage.sigma.data_ptr()
         b.idx, b.idx_offset, b.batch = indices.data_ptr(), int(offset), self.batch
         b.obs_dim, b.critic_obs_dim, b.num_actions = obs.shape[-1], cobs.shape[-1], storage.actions.shape[-1]
+        b.actor_norm, b.critic_norm = self.norm_a, self.norm_c  # (raw storage rows, normalized in the gather)
         pol = self.alg.policy
         _check(lib().zbp_minibatch(C.byref(self.na), C.byref(self.nc), _p(pol.std), _p(pol.std.grad), C.byref(b),
                                    C.byref(self.loss), _p(self.ws), _p(self.stats), self._stream()), "zbp_minibatch")
@@ -312,6 +342,7 @@ class FusedUpdate:
         io.st_log_prob, io.st_mu = storage.actions_log_prob[k].data_ptr(), storage.mu[k].data_ptr()
         io.st_sigma = storage.sigma[k].data_ptr()
         io.rows, io.obs_dim, io.critic_obs_dim, io.num_actions = n, obs.shape[-1], critic_obs.shape[-1], na
+        io.actor_norm, io.critic_norm = self.norm_a, self.norm_c
         _check(lib().zbp_act(C.byref(self.na), C.byref(self.nc), _p(self.alg.policy.std), C.byref(io), _p(self.ws),
                              self.batch, self._stream()), "zbp_act")
         return self._act_out
@@ -331,6 +362,19 @@ class FusedUpdate:
                                   _p(ep_stats), rewards.shape[0], self._stream()), "zbp_env_post")
         self._tout = tout  # (alive until the stream has consumed it)
         storage.step += 1
+
+    def norm_update(self, obs: torch.Tensor, critic_obs: torch.Tensor) -> None:
+        """ActorCritic.update_normalization on zbp_norm_update (two launches, no host sync), called
+        after the env step on its observations; nothing is launched when no normalizer is on."""
+        if not (self.norm_a.mean or self.norm_c.mean):
+            return
+        rows = obs.shape[0]
+        if getattr(self, "_norm_rows", None) != rows:
+            self._norm_scratch = torch.zeros(int(lib().zbp_norm_scratch_floats(rows)), device=obs.device)
+            self._norm_rows = rows
+        obs, critic_obs = obs.contiguous(), critic_obs.contiguous()
+        _check(lib().zbp_norm_update(C.byref(self.norm_a), C.byref(self.norm_c), _p(obs), _p(critic_obs), rows,
+                                     _p(self._norm_scratch), self._stream()), "zbp_norm_update")
 
     def rebind(self) -> None:
         """After parameters or optimizer state were replaced (checkpoint load)."""

@@ -28,6 +28,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .normalizer import EmpiricalNormalization
+
 _ACT = {"elu": nn.ELU, "relu": nn.ReLU, "tanh": nn.Tanh, "selu": nn.SELU, "lrelu": nn.LeakyReLU}
 
 
@@ -88,17 +90,26 @@ class ActorCritic(nn.Module):
 
     def __init__(self, num_actor_obs: int, num_critic_obs: int, num_actions: int,
                  actor_hidden_dims=(128, 128, 128), critic_hidden_dims=(128, 128, 128),
-                 activation: str = "elu", init_noise_std: float = 1.0, **_):
+                 activation: str = "elu", init_noise_std: float = 1.0, actor_obs_normalization: bool = False,
+                 critic_obs_normalization: bool = False, **_):
         super().__init__()
         self.actor = _mlp(num_actor_obs, list(actor_hidden_dims), num_actions, activation)
         self.critic = _mlp(num_critic_obs, list(critic_hidden_dims), 1, activation)
+        # rsl_rl 3.x: EmpiricalNormalization in front of a net, or Identity (no state-dict keys, so
+        # checkpoints written without normalization load unchanged)
+        self.actor_obs_normalization = bool(actor_obs_normalization)
+        self.critic_obs_normalization = bool(critic_obs_normalization)
+        self.actor_obs_normalizer = (EmpiricalNormalization(num_actor_obs) if actor_obs_normalization
+                                     else nn.Identity())
+        self.critic_obs_normalizer = (EmpiricalNormalization(num_critic_obs) if critic_obs_normalization
+                                      else nn.Identity())
         self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
         self.distribution: torch.distributions.Normal | None = None
         torch.distributions.Normal.set_default_validate_args(False)
 
     # -- rsl_rl interface
     def update_distribution(self, obs: torch.Tensor) -> None:
-        mean = self.actor(obs)
+        mean = self.actor(self.actor_obs_normalizer(obs))
         self.distribution = torch.distributions.Normal(mean, mean * 0.0 + self.std)
 
     def act(self, obs: torch.Tensor) -> torch.Tensor:
@@ -109,10 +120,18 @@ class ActorCritic(nn.Module):
         return d.mean + d.stddev * torch.randn_like(d.mean)
 
     def act_inference(self, obs: torch.Tensor) -> torch.Tensor:
-        return self.actor(obs)
+        return self.actor(self.actor_obs_normalizer(obs))
 
     def evaluate(self, obs: torch.Tensor) -> torch.Tensor:
-        return self.critic(obs)
+        return self.critic(self.critic_obs_normalizer(obs))
+
+    def update_normalization(self, obs: torch.Tensor, critic_obs: torch.Tensor | None = None) -> None:
+        """rsl_rl: the rollout feeds every post-step observation to the normalizers that are on (the
+        storage keeps raw observations; the update normalizes them with the statistics of its time)."""
+        if self.actor_obs_normalization:
+            self.actor_obs_normalizer.update(obs)
+        if self.critic_obs_normalization:
+            self.critic_obs_normalizer.update(obs if critic_obs is None else critic_obs)
 
     def get_actions_log_prob(self, actions: torch.Tensor) -> torch.Tensor:
         return self.distribution.log_prob(actions).sum(dim=-1)

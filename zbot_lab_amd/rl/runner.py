@@ -23,6 +23,7 @@ import contextlib
 import os
 import statistics
 import time
+import warnings
 from collections import deque
 
 import torch
@@ -66,9 +67,10 @@ class OnPolicyRunner:
         num_obs = obs.shape[1]
         self.alg_cfg.pop("class_name", None)
         self.policy_cfg.pop("class_name", None)
-        for k in ("actor_obs_normalization", "critic_obs_normalization"):
-            if self.policy_cfg.pop(k, False):
-                raise NotImplementedError(f"{k}=True (rsl_rl EmpiricalNormalization) is not implemented")
+        if train_cfg.get("empirical_normalization"):  # rsl_rl's legacy flag: both normalizers
+            warnings.warn("empirical_normalization is deprecated: set the policy's actor_obs_normalization / "
+                          "critic_obs_normalization", DeprecationWarning, stacklevel=2)
+            self.policy_cfg["actor_obs_normalization"] = self.policy_cfg["critic_obs_normalization"] = True
         policy = ActorCritic(num_obs, num_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
         self.alg = PPO(policy, device=self.device, multi_gpu_cfg=self.multi_gpu_cfg, **self.alg_cfg)
         self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
@@ -205,6 +207,7 @@ class OnPolicyRunner:
                 fr.env_post(st, rewards.to(self.device), dones.to(self.device),
                             None if tout is None else tout.to(self.device), self.alg.gamma, self.cur_rew, self.cur_len,
                             self.ep_stats)
+                fr.norm_update(obs, obs)  # (no launch when no normalizer is on)
                 self._accumulate_log(extras)
             self._extras = extras
             return obs
@@ -214,6 +217,8 @@ class OnPolicyRunner:
             obs = _policy_obs(obs_d).to(self.device)
             rewards, dones = rewards.to(self.device), dones.to(self.device)
             self.alg.process_env_step(rewards, dones, extras)
+            # rsl_rl: the normalizers see the post-step observation before the next act
+            self.alg.policy.update_normalization(obs, obs)
             self.cur_rew += rewards
             self.cur_len += 1
             d = dones > 0
