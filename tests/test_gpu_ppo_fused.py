@@ -41,7 +41,8 @@ def _alg(hidden, obs_dim=23, act=6, envs=512, steps=24, seed=0):
 
 
 def _torch_minibatch(alg, i):
-    """update_steps' loss for minibatch i of the first epoch, backward into .grad (autograd)."""
+    """update_steps' loss for minibatch i of the first epoch, backward into .grad (autograd).
+    tests/ppo_cases.py torch_minibatch is the same with the plain value loss too: keep them in step."""
     import torch
     gen = alg.storage.mini_batch_generator(alg.num_mini_batches, 1, alg.mb_indices)
     for k, mbt in enumerate(gen):
@@ -72,7 +73,8 @@ def _torch_minibatch(alg, i):
 @pytest.mark.parametrize("hidden", [[128, 128, 128], [256, 256, 128]], ids=["v2-nets", "standup-nets"])
 def test_fused_minibatch_gradients_match_autograd(gpu, hidden, rows, monkeypatch):
     """rows: the register-resident row kernel (k_rows_reg, these shapes' default) or the LDS one
-    (ZBP_ROWS=lds, every other shape)."""
+    (ZBP_ROWS=lds, every other shape). The std is 1.0 for every action here; a distinct std per action:
+    tests/test_gpu_ppo_shapes.py."""
     import torch
     from zbot_lab_amd.rl import fused
     if rows == "lds":
@@ -210,7 +212,8 @@ def test_fused_act_matches_torch_policy(gpu, hidden, rows, monkeypatch):
     same standard-normal draw: actions, mu, sigma, log-probabilities, values and the observations in
     the storage slot (fp32 summation-order tolerances); rows not a multiple of 32 included. rows: the
     register-resident forward (k_act_reg, rollouts of >= 4096 rows; reg-small: forced at 200 rows) or
-    the LDS one (ZBP_ACT=lds, and every smaller rollout)."""
+    the LDS one (ZBP_ACT=lds, and every smaller rollout). The std is 1.0 for every action here; a
+    distinct std per action: tests/test_gpu_ppo_shapes.py."""
     import torch
     from zbot_lab_amd.rl import fused
     if rows == "lds":
