@@ -28,9 +28,16 @@ extern "C" {
 
 #define ZBP_MAX_LAYERS 4 /* linear layers per MLP (3 hidden + output, the rsl_rl cfgs here) */
 
-/* One MLP (torch nn.Sequential of Linear / ELU): layer l maps dim[l] -> dim[l+1]; ELU after every
- * layer but the last. Limits: dim[0] <= 32 (observations), hidden dims multiples of 32 up to 256,
- * output dim <= 32. */
+/* The activation after every layer of an MLP but the last (rsl_rl's `activation`), with torch's default
+ * constants: ELU alpha = 1; SELU lambda = 1.0507009873554805, alpha = 1.6732632423543772; LeakyReLU
+ * negative slope 0.01. The backward passes write each derivative from the stored OUTPUT x of the
+ * activation: ELU x > 0 ? 1 : x + 1; ReLU x > 0; Tanh 1 - x^2; SELU x > 0 ? lambda : x + lambda alpha;
+ * LeakyReLU x > 0 ? 1 : 0.01. */
+enum { ZBP_ACT_ELU = 0, ZBP_ACT_RELU, ZBP_ACT_TANH, ZBP_ACT_SELU, ZBP_ACT_LRELU };
+
+/* One MLP (torch nn.Sequential of Linear / activation): layer l maps dim[l] -> dim[l+1]; the
+ * activation after every layer but the last. Limits: dim[0] <= 32 (observations), hidden dims
+ * multiples of 32 up to 256, output dim <= 32. */
 typedef struct {
   int32_t n_layers;
   int32_t dim[ZBP_MAX_LAYERS + 1];
@@ -38,6 +45,9 @@ typedef struct {
   const float* b[ZBP_MAX_LAYERS]; /* Linear.bias [dim[l+1]] */
   float* gw[ZBP_MAX_LAYERS];      /* their .grad buffers (overwritten by zbp_minibatch) */
   float* gb[ZBP_MAX_LAYERS];
+  int32_t activation; /* ZBP_ACT_*; a zeroed field is ELU. Actor and critic must agree (rsl_rl has one
+                         `activation` for both nets); any other value, or a mixed pair, is refused by
+                         every entry point before any launch (zbp_workspace_floats returns < 0) */
 } zbp_net;
 
 /* Empirical observation normalization (rsl_rl EmpiricalNormalization; zbot_lab_amd/rl/normalizer.py):
@@ -81,6 +91,11 @@ typedef struct {
 typedef struct {
   float clip_param, value_loss_coef, entropy_coef;
   int32_t use_clipped_value_loss;
+  int32_t log_std; /* rsl_rl noise_std_type "log": std_param holds log sigma and sigma = exp(std_param) in
+                      the log-prob, the KL and the mean / std gradients; std_grad receives dL / d log sigma =
+                      sigma dL / d sigma (the entropy bonus contributes -entropy_coef per action) and the
+                      entropy statistic takes the parameter itself as log sigma. 0 ("scalar"): std_param is
+                      sigma */
 } zbp_loss_cfg;
 
 /* Workspace floats for nets of these shapes and minibatch size (the caller allocates one float
@@ -161,6 +176,8 @@ typedef struct {
   int32_t noise_seed;       /* (noise == NULL) the caller's stream, e.g. one per rank */
   zbp_obs_norm actor_norm;  /* the actor sees normalized obs (mean == NULL: none); st_obs stays raw */
   zbp_obs_norm critic_norm; /* the critic sees normalized critic_obs; st_critic_obs stays raw */
+  int32_t log_std;          /* std_param holds log sigma (zbp_loss_cfg.log_std): the draw and the log-probability
+                               use sigma = exp(std_param), and st_sigma receives sigma */
 } zbp_act_io;
 int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param, const zbp_act_io* io, float* ws,
             int32_t batch, void* stream);

@@ -5,7 +5,8 @@
 //
 //   k_pack       padded / transposed / lane-ordered weight images in the workspace
 //   k_rows_reg   (the shipped net shapes) one wave per 16 minibatch rows, activations in registers:
-//                gather through the permutation, actor forward (Linear + ELU on
+//                gather through the permutation, actor forward (Linear + the nets' activation, ELU in
+//                every shipped cfg, relu / tanh / selu / lrelu as template instantiations, on
 //                v_mfma_f32_16x16x4_f32, the previous layer's accumulators as the B operand, weights
 //                shared by the workgroup's four waves through LDS), Gaussian log-prob / KL / clipped
 //                surrogate and its gradient, actor backward dX; then the critic forward, clipped value
@@ -67,6 +68,7 @@ __host__ __device__ __forceinline__ int64_t rbo(int P, int f, int i) { return ((
 // one net in the workspace: dims and float offsets of its images and row buffers
 struct NetW {
   int L, d[MAXL + 1], p[MAXL + 1];
+  int act;                               // ZBP_ACT_* (the LDS kernels branch on it; the register kernels are instantiated per value)
   int64_t wp[MAXL], wt[MAXL], bp[MAXL];  // padded weights [p(l+1)][p(l)], transposed [p(l)][p(l+1)], bias [p(l+1)]
   int64_t wr[MAXL], wtr[MAXL];           // the same in k_rows_reg's lane order (forward / backward A operands)
   int64_t x[MAXL], dz[MAXL];             // row buffers: X_l [B][p(l)], dZ_l [B][p(l+1)]
@@ -115,6 +117,7 @@ Layout make_layout(const zbp_net* a, const zbp_net* c, int B) {
   for (int k = 0; k < 2; ++k) {
     NetW& w = lo.n[k];
     w.L = nets[k]->n_layers;
+    w.act = nets[k]->activation;
     for (int l = 0; l <= w.L; ++l) { w.d[l] = nets[k]->dim[l]; w.p[l] = pad32(w.d[l]); }
     for (int l = 0; l < w.L; ++l) {
       w.wp[l] = take((int64_t)w.p[l + 1] * w.p[l]);
@@ -182,6 +185,15 @@ const char* check_net(const zbp_net* n) {
   if (n->dim[n->n_layers] < 1 || n->dim[n->n_layers] > 32) return "output dim must be 1..32";
   for (int l = 0; l < n->n_layers; ++l)
     if (!n->w[l] || !n->b[l]) return "null weight / bias";
+  if (n->activation < ZBP_ACT_ELU || n->activation > ZBP_ACT_LRELU) return "activation must be one of ZBP_ACT_*";
+  return nullptr;
+}
+// both nets of a call: each within the limits, and one activation for the pair (rsl_rl has one
+// `activation`; the paired register kernels are instantiated per activation)
+const char* check_nets(const zbp_net* a, const zbp_net* c) {
+  if (const char* e = check_net(a)) return e;
+  if (const char* e = check_net(c)) return e;
+  if (a->activation != c->activation) return "actor and critic must have the same activation";
   return nullptr;
 }
 
@@ -195,6 +207,54 @@ const char* check_norm(const zbp_obs_norm* n, int dim) {
 
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+// The hidden layers' activation (zbp_net.activation, torch's default constants, the expressions of
+// ATen's kernels) and its derivative written from the OUTPUT x = act(z): the backward passes hold only
+// the stored X_l. kAct is a compile-time value in the register kernels (the ELU instantiations keep
+// their code and register budget); the LDS kernels switch on a uniform runtime value (act_rt / dact_rt).
+constexpr float kSeluScale = 1.0507009873554805f, kSeluAlpha = 1.6732632423543772f;
+constexpr float kSeluNeg = kSeluScale * kSeluAlpha;
+constexpr float kLreluSlope = 0.01f;
+template <int kAct>
+__device__ __forceinline__ float act_f(float v) {
+  if (kAct == ZBP_ACT_RELU) return v > 0.f ? v : 0.f;
+  if (kAct == ZBP_ACT_TANH) return tanhf(v);
+  if (kAct == ZBP_ACT_SELU) return v > 0.f ? kSeluScale * v : kSeluNeg * (expf(v) - 1.f);
+  if (kAct == ZBP_ACT_LRELU) return v > 0.f ? v : kLreluSlope * v;
+  return v > 0.f ? v : expf(v) - 1.f;  // ELU(alpha = 1), as ATen's elu kernel
+}
+template <int kAct>
+__device__ __forceinline__ float dact_f(float x) {
+  if (kAct == ZBP_ACT_RELU) return x > 0.f ? 1.f : 0.f;
+  if (kAct == ZBP_ACT_TANH) return 1.f - x * x;
+  if (kAct == ZBP_ACT_SELU) return x > 0.f ? kSeluScale : x + kSeluNeg;  // lambda alpha exp(z) = x + lambda alpha for z <= 0
+  if (kAct == ZBP_ACT_LRELU) return x > 0.f ? 1.f : kLreluSlope;
+  return x > 0.f ? 1.f : x + 1.f;  // ELU'(z) = exp(z) = x + 1 for z <= 0
+}
+__device__ __forceinline__ float act_rt(int act, float v) {
+  switch (act) {
+    case ZBP_ACT_RELU: return act_f<ZBP_ACT_RELU>(v);
+    case ZBP_ACT_TANH: return act_f<ZBP_ACT_TANH>(v);
+    case ZBP_ACT_SELU: return act_f<ZBP_ACT_SELU>(v);
+    case ZBP_ACT_LRELU: return act_f<ZBP_ACT_LRELU>(v);
+    default: return act_f<ZBP_ACT_ELU>(v);
+  }
+}
+__device__ __forceinline__ float dact_rt(int act, float x) {
+  switch (act) {
+    case ZBP_ACT_RELU: return dact_f<ZBP_ACT_RELU>(x);
+    case ZBP_ACT_TANH: return dact_f<ZBP_ACT_TANH>(x);
+    case ZBP_ACT_SELU: return dact_f<ZBP_ACT_SELU>(x);
+    case ZBP_ACT_LRELU: return dact_f<ZBP_ACT_LRELU>(x);
+    default: return dact_f<ZBP_ACT_ELU>(x);
+  }
+}
+// the Gaussian's sigma and log sigma of one action from the noise parameter p: sigma itself
+// (zbp_loss_cfg.log_std == 0), or log sigma (rsl_rl noise_std_type "log": sigma = exp(p), log sigma = p)
+__device__ __forceinline__ void sigma_of(float p, int log_std, float& s, float& ls) {
+  if (log_std) { s = expf(p); ls = p; }
+  else { s = p; ls = logf(p); }
 }
 
 // C[32 rows][32 cols] = sum_k A[r][k] B[k][c] over k < kp (kp a multiple of 32): A row-major in LDS
@@ -333,7 +393,7 @@ __device__ void net_forward_t(const NetW& w, float* ws, int B, const int* lds_x,
           if (last) {
             lds[lds_out + i * 33 + n] = v[u];
           } else {
-            v[u] = v[u] > 0.f ? v[u] : expf(v[u]) - 1.f;  // ELU(alpha = 1), as ATen's elu kernel
+            v[u] = act_rt(w.act, v[u]);
             lds[lds_x[l + 1] + i * (P1 + 4) + n] = v[u];
           }
         }
@@ -367,7 +427,7 @@ __device__ void net_backward(const RowArgs& A, const NetW& w, float* lds, int ro
         for (int u = 0; u < 4; ++u) {
           const int i = 8 * q + 4 * h + u;
           const float x = xs[i * (P0 + 4) + k];
-          g[u] = acc[4 * q + u] * (x > 0.f ? 1.f : x + 1.f);  // ELU'(z) = exp(z) = x + 1 for z <= 0
+          g[u] = acc[4 * q + u] * dact_rt(w.act, x);
           xs[i * (P0 + 4) + k] = g[u];
         }
         *reinterpret_cast<float4*>(A.ws + w.dz[l - 1] + rbo(P0, k, row0 + 8 * q + 4 * h)) =
@@ -431,9 +491,11 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
       const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
       float lp = 0.f;
       for (int a = 0; a < NA; ++a) {
-        const float mu = lds[A.lds_out + i * 33 + a], s = A.std_param[a];
+        const float mu = lds[A.lds_out + i * 33 + a];
+        float s, ls;
+        sigma_of(A.std_param[a], A.lc.log_std, s, ls);
         const float x = bt.actions[row * NA + a], diff = x - mu;
-        lp += -(diff * diff) / (2.f * (s * s)) - logf(s) - kLog2Pi;
+        lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
         const float os = bt.sigma[row * NA + a], om = bt.mu[row * NA + a];
         kl += logf(s / os + 1e-5f) + (os * os + (om - mu) * (om - mu)) / (2.f * (s * s)) - 0.5f;
       }
@@ -450,7 +512,8 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
       for (int a = 0; a < Pout; ++a) {
         float d = 0.f;
         if (a < NA) {
-          const float mu = lds[A.lds_out + i * 33 + a], s = A.std_param[a];
+          const float mu = lds[A.lds_out + i * 33 + a];
+          const float s = A.lc.log_std ? expf(A.std_param[a]) : A.std_param[a];
           const float diff = bt.actions[row * NA + a] - mu;
           d = g * diff / (s * s);
 #pragma unroll
@@ -529,7 +592,8 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
 // + 16 output tiles (128 registers) live, so two waves share each SIMD and cover each other's
 // epilogues (bias, ELU, the row-buffer stores) and memory waits. The workgroup's four waves share
 // the weights through LDS (double-buffered 32 KB chunks of 32 blocks, one barrier per chunk). X_l
-// and dZ_l go to HBM octet-blocked (rbo) for k_wgrad; the backward pass reads X_l back for ELU'.
+// and dZ_l go to HBM octet-blocked (rbo) for k_wgrad; the backward pass reads X_l back for the
+// activation's derivative (written from the output, dact_f). kAct: the activation, a compile-time value.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef f32x4 Tile;
 
@@ -612,9 +676,9 @@ __device__ __forceinline__ void rr_layer(const float* __restrict__ img, float4* 
   }
 }
 
-// forward layer l: + bias, ELU (hidden layers: also X_{l+1} to HBM)
+// forward layer l: + bias, the activation kAct (hidden layers: also X_{l+1} to HBM)
 // (NBN > 0: the next layer's image `next` has NBN blocks; its chunk 0 is fetched before this epilogue)
-template <int TI, int TO, bool kLast, bool kStore, int NBN, int CB>
+template <int TI, int TO, bool kLast, bool kStore, int NBN, int CB, int kAct>
 __device__ __forceinline__ void rr_forward(const NetW& w, int l, float* __restrict__ ws, float4* __restrict__ wl, int row0,
                                            const Tile (&in)[TI], Tile (&out)[TO], RrStage<CB>& st, const float* next) {
   const int lo = rr_lane_off(16 * TO);
@@ -630,7 +694,7 @@ __device__ __forceinline__ void rr_forward(const NetW& w, int l, float* __restri
     for (int u = 0; u < 4; ++u) {
       float v = out[o][u] + bv[u];
       if (!kLast) {
-        v = v > 0.f ? v : expf(v) - 1.f;  // ELU(alpha = 1), as ATen's elu kernel
+        v = act_f<kAct>(v);
         if (kStore) rr_at(xb, o, u)[lo] = v;
       }
       out[o][u] = v;
@@ -638,8 +702,8 @@ __device__ __forceinline__ void rr_forward(const NetW& w, int l, float* __restri
   }
 }
 
-// backward through layer l >= 1: dZ_{l-1} = (W_l^T dZ_l) * ELU'(X_l), to registers and HBM
-template <int TI, int TO, int NBN, int CB>
+// backward through layer l >= 1: dZ_{l-1} = (W_l^T dZ_l) * act'(X_l) (from the output, dact_f), to registers and HBM
+template <int TI, int TO, int NBN, int CB, int kAct>
 __device__ __forceinline__ void rr_backward(const NetW& w, int l, float* __restrict__ ws, float4* __restrict__ wl, int row0,
                                             const Tile (&dz)[TI], Tile (&out)[TO], RrStage<CB>& st, const float* next) {
   const int lo = rr_lane_off(16 * TO);
@@ -660,7 +724,7 @@ __device__ __forceinline__ void rr_backward(const NetW& w, int l, float* __restr
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float x = o < NPRE ? xl[o][u] : rr_at(xb, o, u)[lo];
-      const float gr = out[o][u] * (x > 0.f ? 1.f : x + 1.f);  // ELU'(z) = exp(z) = x + 1 for z <= 0
+      const float gr = out[o][u] * dact_f<kAct>(x);
       out[o][u] = gr;
       rr_at(db, o, u)[lo] = gr;
     }
@@ -709,7 +773,7 @@ __device__ __forceinline__ float rr_feat_sum(float v) {
 }
 
 constexpr int RR_TR = 16;  // rows per wave
-template <int T1, int T2, int T3, bool kNorm>
+template <int T1, int T2, int T3, bool kNorm, int kAct>
 __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   constexpr int CB = rr_cb<T1>();
   __shared__ float4 wl[2 * CB * 64];
@@ -749,10 +813,10 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   {
     Tile x0[2], x1[T1], x2[T2], x3[T3];
     rr_gather<kNorm>(wa, ws, row0, bt.obs, bt.obs_dim, bt.actor_norm, row, x0);
-    rr_forward<2, T1, false, true, T1 * T2, CB>(wa, 0, ws, wl, row0, x0, x1, wst, ws + wa.wr[1]);
-    rr_forward<T1, T2, false, true, T2 * T3, CB>(wa, 1, ws, wl, row0, x1, x2, wst, ws + wa.wr[2]);
-    rr_forward<T2, T3, false, true, T3 * 2, CB>(wa, 2, ws, wl, row0, x2, x3, wst, ws + wa.wr[3]);
-    rr_forward<T3, 2, true, true, 2 * T3, CB>(wa, 3, ws, wl, row0, x3, z, wst, ws + wa.wtr[3]);
+    rr_forward<2, T1, false, true, T1 * T2, CB, kAct>(wa, 0, ws, wl, row0, x0, x1, wst, ws + wa.wr[1]);
+    rr_forward<T1, T2, false, true, T2 * T3, CB, kAct>(wa, 1, ws, wl, row0, x1, x2, wst, ws + wa.wr[2]);
+    rr_forward<T2, T3, false, true, T3 * 2, CB, kAct>(wa, 2, ws, wl, row0, x2, x3, wst, ws + wa.wr[3]);
+    rr_forward<T3, 2, true, true, 2 * T3, CB, kAct>(wa, 3, ws, wl, row0, x3, z, wst, ws + wa.wtr[3]);
   }
   {
     // lane (r, g) holds actions 4 g + u (tile 0) and 16 + 4 g + u (tile 1) of row r
@@ -763,10 +827,12 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
       const int n = 16 * (j >> 2) + 4 * gq + (j & 3);
       diff[j] = 0.f;
       if (n < NA) {
-        const float mu = z[j >> 2][j & 3], s = A.std_param[n];
+        const float mu = z[j >> 2][j & 3];
+        float s, ls;
+        sigma_of(A.std_param[n], A.lc.log_std, s, ls);
         const float d = act_in[j & 3] - mu;  // (n < NA only in tile 0: j < 4)
         diff[j] = d;
-        lp += -(d * d) / (2.f * (s * s)) - logf(s) - kLog2Pi;
+        lp += -(d * d) / (2.f * (s * s)) - ls - kLog2Pi;
         const float os = sig_in[j & 3], om = mu_in[j & 3];
         kl += logf(s / os + 1e-5f) + (os * os + (om - mu) * (om - mu)) / (2.f * (s * s)) - 0.5f;
       }
@@ -788,7 +854,7 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
       const int n = 16 * (j >> 2) + 4 * gq + (j & 3);
       float d = 0.f, sg = 0.f;
       if (n < NA) {
-        const float s = A.std_param[n];
+        const float s = A.lc.log_std ? expf(A.std_param[n]) : A.std_param[n];
         d = g * diff[j] / (s * s);
         sg = g * (diff[j] * diff[j] / (s * s * s) - 1.f / s);
       }
@@ -806,9 +872,9 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   }
   {
     Tile d3[T3], d2[T2], d1[T1];
-    rr_backward<2, T3, T3 * T2, CB>(wa, 3, ws, wl, row0, dz, d3, wst, ws + wa.wtr[2]);
-    rr_backward<T3, T2, T2 * T1, CB>(wa, 2, ws, wl, row0, d3, d2, wst, ws + wa.wtr[1]);
-    rr_backward<T2, T1, 0, CB>(wa, 1, ws, wl, row0, d2, d1, wst, nullptr);
+    rr_backward<2, T3, T3 * T2, CB, kAct>(wa, 3, ws, wl, row0, dz, d3, wst, ws + wa.wtr[2]);
+    rr_backward<T3, T2, T2 * T1, CB, kAct>(wa, 2, ws, wl, row0, d3, d2, wst, ws + wa.wtr[1]);
+    rr_backward<T2, T1, 0, CB, kAct>(wa, 1, ws, wl, row0, d2, d1, wst, nullptr);
   }
   } else {
   const float tv_in = bt.values[row], ret_in = bt.returns[row];
@@ -817,10 +883,10 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   {
     Tile x0[2], x1[T1], x2[T2], x3[T3];
     rr_gather<kNorm>(wc, ws, row0, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, row, x0);
-    rr_forward<2, T1, false, true, T1 * T2, CB>(wc, 0, ws, wl, row0, x0, x1, wst, ws + wc.wr[1]);
-    rr_forward<T1, T2, false, true, T2 * T3, CB>(wc, 1, ws, wl, row0, x1, x2, wst, ws + wc.wr[2]);
-    rr_forward<T2, T3, false, true, T3 * 2, CB>(wc, 2, ws, wl, row0, x2, x3, wst, ws + wc.wr[3]);
-    rr_forward<T3, 2, true, true, 2 * T3, CB>(wc, 3, ws, wl, row0, x3, z, wst, ws + wc.wtr[3]);
+    rr_forward<2, T1, false, true, T1 * T2, CB, kAct>(wc, 0, ws, wl, row0, x0, x1, wst, ws + wc.wr[1]);
+    rr_forward<T1, T2, false, true, T2 * T3, CB, kAct>(wc, 1, ws, wl, row0, x1, x2, wst, ws + wc.wr[2]);
+    rr_forward<T2, T3, false, true, T3 * 2, CB, kAct>(wc, 2, ws, wl, row0, x2, x3, wst, ws + wc.wr[3]);
+    rr_forward<T3, 2, true, true, 2 * T3, CB, kAct>(wc, 3, ws, wl, row0, x3, z, wst, ws + wc.wtr[3]);
   }
   {
     const float v = __shfl(z[0][0], r), tv = tv_in, ret = ret_in, clip = A.lc.clip_param;
@@ -846,9 +912,9 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   }
   {
     Tile d3[T3], d2[T2], d1[T1];
-    rr_backward<2, T3, T3 * T2, CB>(wc, 3, ws, wl, row0, dz, d3, wst, ws + wc.wtr[2]);
-    rr_backward<T3, T2, T2 * T1, CB>(wc, 2, ws, wl, row0, d3, d2, wst, ws + wc.wtr[1]);
-    rr_backward<T2, T1, 0, CB>(wc, 1, ws, wl, row0, d2, d1, wst, nullptr);
+    rr_backward<2, T3, T3 * T2, CB, kAct>(wc, 3, ws, wl, row0, dz, d3, wst, ws + wc.wtr[2]);
+    rr_backward<T3, T2, T2 * T1, CB, kAct>(wc, 2, ws, wl, row0, d3, d2, wst, ws + wc.wtr[1]);
+    rr_backward<T2, T1, 0, CB, kAct>(wc, 1, ws, wl, row0, d2, d1, wst, nullptr);
   }
   }
 }
@@ -996,6 +1062,7 @@ struct ReduceArgs {
   float* std_grad;
   float* stats;
   float entropy_coef;
+  int log_std;  // std_param holds log sigma (zbp_loss_cfg.log_std)
   const float* ws;
   int64_t part, rstats;
   float* norm2;  // [wtiles + 1]: each tile's sum of squared gradients (the last: the std's), for zbp_optimizer_step
@@ -1048,14 +1115,19 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
       for (int q = 0; q < NSTAT; ++q) tot[q] = red[0][q];
       const float invB = 1.f / (float)A.batch;
       float ent = 0.f;
-      for (int a = 0; a < A.num_actions; ++a) ent += 0.5f + 0.91893853320467274178f + logf(A.std_param[a]);
+      // (log std: the parameter is log sigma)
+      for (int a = 0; a < A.num_actions; ++a)
+        ent += 0.5f + 0.91893853320467274178f + (A.log_std ? A.std_param[a] : logf(A.std_param[a]));
       A.stats[0] = tot[2] * invB;  // kl mean
       A.stats[1] = tot[1] * invB;  // value loss
       A.stats[2] = tot[0] * invB;  // surrogate loss
       A.stats[3] = ent;            // entropy (every row's)
       float ss = 0.f;
       for (int a = 0; a < A.num_actions; ++a) {
-        const float g = tot[3 + a] - A.entropy_coef / A.std_param[a];
+        // tot[3 + a] = dL / d sigma of the surrogate; log std: dL / d log sigma = sigma dL / d sigma, and the
+        // entropy bonus -entropy_coef log sigma contributes -entropy_coef
+        const float g = A.log_std ? expf(A.std_param[a]) * tot[3 + a] - A.entropy_coef
+                                  : tot[3 + a] - A.entropy_coef / A.std_param[a];
         A.std_grad[a] = g;
         ss += g * g;
       }
@@ -1194,6 +1266,7 @@ struct ActArgs {
   int noise_step;
   uint32_t noise_seed;
   int obs_dim, cobs_dim, na, rows;
+  int log_std;  // std_param holds log sigma (zbp_act_io.log_std)
   float *actions, *s_obs, *s_cobs, *s_act, *s_val, *s_lp, *s_mu, *s_sig;
   int lds_x[MAXL], lds_out;
   zbp_obs_norm nrm[2];  // the actor's / critic's observation normalizer (mean == nullptr: none)
@@ -1242,9 +1315,11 @@ __global__ __launch_bounds__(256) void k_act(ActArgs A) {
     const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
     float lp = 0.f;
     for (int a = 0; a < A.na; ++a) {
-      const float mu = lds[A.lds_out + tid * 33 + a], s = A.std_param[a];
+      const float mu = lds[A.lds_out + tid * 33 + a];
+      float s, ls;
+      sigma_of(A.std_param[a], A.log_std, s, ls);
       const float x = mu + s * noise_at(A, row, a), diff = x - mu;
-      lp += -(diff * diff) / (2.f * (s * s)) - logf(s) - kLog2Pi;
+      lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
       A.actions[row * A.na + a] = x;
       A.s_act[row * A.na + a] = x;
       A.s_mu[row * A.na + a] = mu;
@@ -1260,7 +1335,7 @@ __global__ __launch_bounds__(256) void k_act(ActArgs A) {
 
 // k_act on the register-resident forward (k_rows_reg's shapes): one wave per 16 rows, the weights
 // shared through LDS
-template <int T1, int T2, int T3, bool kNorm>
+template <int T1, int T2, int T3, bool kNorm, int kAct>
 #ifndef ZBP_ACT_REG_MIN
 #define ZBP_ACT_REG_MIN 4096
 #endif
@@ -1293,10 +1368,10 @@ __global__ __launch_bounds__(RR_WG, 2) void k_act_reg(ActArgs A) {
       x0[j >> 2][j & 3] = (kNorm && A.nrm[net].mean && ok && k < dim) ? obs_normalize(A.nrm[net], k, v) : v;
       if (ok && k < dim) st[k] = v;
     }
-    rr_forward<2, T1, false, false, T1 * T2, CB>(w, 0, A.ws, wl, 0, x0, x1, wst, A.ws + w.wr[1]);
-    rr_forward<T1, T2, false, false, T2 * T3, CB>(w, 1, A.ws, wl, 0, x1, x2, wst, A.ws + w.wr[2]);
-    rr_forward<T2, T3, false, false, T3 * 2, CB>(w, 2, A.ws, wl, 0, x2, x3, wst, A.ws + w.wr[3]);
-    rr_forward<T3, 2, true, false, 0, CB>(w, 3, A.ws, wl, 0, x3, z, wst, nullptr);
+    rr_forward<2, T1, false, false, T1 * T2, CB, kAct>(w, 0, A.ws, wl, 0, x0, x1, wst, A.ws + w.wr[1]);
+    rr_forward<T1, T2, false, false, T2 * T3, CB, kAct>(w, 1, A.ws, wl, 0, x1, x2, wst, A.ws + w.wr[2]);
+    rr_forward<T2, T3, false, false, T3 * 2, CB, kAct>(w, 2, A.ws, wl, 0, x2, x3, wst, A.ws + w.wr[3]);
+    rr_forward<T3, 2, true, false, 0, CB, kAct>(w, 3, A.ws, wl, 0, x3, z, wst, nullptr);
     if (net == 0) {
       // lane (r, g) holds actions 4 g + u and 16 + 4 g + u of row r
       const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
@@ -1305,9 +1380,11 @@ __global__ __launch_bounds__(RR_WG, 2) void k_act_reg(ActArgs A) {
       for (int j = 0; j < 8; ++j) {
         const int n = 16 * (j >> 2) + 4 * gq + (j & 3);
         if (ok && n < na) {
-          const float mu = z[j >> 2][j & 3], s = A.std_param[n];
+          const float mu = z[j >> 2][j & 3];
+          float s, ls;
+          sigma_of(A.std_param[n], A.log_std, s, ls);
           const float x = mu + s * noise_at(A, row, n), diff = x - mu;
-          lp += -(diff * diff) / (2.f * (s * s)) - logf(s) - kLog2Pi;
+          lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
           A.actions[row * na + n] = x;
           A.s_act[row * na + n] = x;
           A.s_mu[row * na + n] = mu;
@@ -1328,7 +1405,7 @@ __global__ __launch_bounds__(RR_WG, 2) void k_act_reg(ActArgs A) {
 // per layer); each wave reads its own output tiles' weight blocks from L2 (no staging). At 4096 rows
 // that is 2048 waves (two per SIMD) with a quarter of k_act_reg's MFMAs each, against k_act_reg's 512
 // waves holding the whole net. Same statement (same per-lane accumulation order within a tile).
-template <int TI, int TO, bool kElu>
+template <int TI, int TO, int kAct>
 __device__ __forceinline__ void as_layer(const float* __restrict__ img, const float* __restrict__ bias,
                                          const Tile (&in)[TI], Tile (&out)[TO], Tile* __restrict__ xs, int wv,
                                          int lane) {
@@ -1362,7 +1439,7 @@ __device__ __forceinline__ void as_layer(const float* __restrict__ img, const fl
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       float v = acc[q][u] + bv[u];
-      if (kElu) v = v > 0.f ? v : expf(v) - 1.f;  // ELU(alpha = 1), as ATen's elu kernel
+      v = act_f<kAct>(v);
       acc[q][u] = v;
     }
     xs[o * 64 + lane] = acc[q];
@@ -1372,7 +1449,7 @@ __device__ __forceinline__ void as_layer(const float* __restrict__ img, const fl
   for (int o = 0; o < TO; ++o) out[o] = xs[o * 64 + lane];
 }
 
-template <int T1, int T2, int T3, bool kNorm>
+template <int T1, int T2, int T3, bool kNorm, int kAct>
 __global__ __launch_bounds__(256, 2) void k_act_split(ActArgs A) {
   static_assert(T1 % 4 == 0 && T2 % 4 == 0 && T3 % 4 == 0, "output tiles split over four waves");
   constexpr int TM = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
@@ -1396,9 +1473,9 @@ __global__ __launch_bounds__(256, 2) void k_act_split(ActArgs A) {
       if (wv == 0 && ok && k < dim) st[k] = v;
     }
   }
-  as_layer<2, T1, true>(A.ws + w.wr[0], A.ws + w.bp[0], x0, x1, xs[0], wv, lane);
-  as_layer<T1, T2, true>(A.ws + w.wr[1], A.ws + w.bp[1], x1, x2, xs[1], wv, lane);
-  as_layer<T2, T3, true>(A.ws + w.wr[2], A.ws + w.bp[2], x2, x3, xs[0], wv, lane);
+  as_layer<2, T1, kAct>(A.ws + w.wr[0], A.ws + w.bp[0], x0, x1, xs[0], wv, lane);
+  as_layer<T1, T2, kAct>(A.ws + w.wr[1], A.ws + w.bp[1], x1, x2, xs[1], wv, lane);
+  as_layer<T2, T3, kAct>(A.ws + w.wr[2], A.ws + w.bp[2], x2, x3, xs[0], wv, lane);
   if (wv != 0) return;
   // the output layer (2 tiles in the image: num_actions <= 13 and the value live in tile 0), wave 0
   Tile z = Tile{};
@@ -1423,9 +1500,11 @@ __global__ __launch_bounds__(256, 2) void k_act_split(ActArgs A) {
     for (int u = 0; u < 4; ++u) {
       const int n = 4 * gq + u;
       if (ok && n < na) {
-        const float mu = z[u], s = A.std_param[n];
+        const float mu = z[u];
+        float s, ls;
+        sigma_of(A.std_param[n], A.log_std, s, ls);
         const float x = mu + s * noise_at(A, row, n), diff = x - mu;
-        lp += -(diff * diff) / (2.f * (s * s)) - logf(s) - kLog2Pi;
+        lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
         A.actions[row * na + n] = x;
         A.s_act[row * na + n] = x;
         A.s_mu[row * na + n] = mu;
@@ -1686,6 +1765,45 @@ int launch_check(const char* what) {
   return e == hipSuccess ? 0 : hip_fail(e, what);
 }
 
+// The register kernels per activation. ELU (every shipped cfg) keeps its two instantiations, with and
+// without the normalizer's code; the other activations have one each, the kNorm one, which tests the
+// normalizer's pointer at run time (half the instantiations to compile).
+template <int T1, int T2, int T3>
+void launch_rows_reg(int act, bool norm, int grid, hipStream_t s, const RowArgs& R) {
+  switch (act) {
+    case ZBP_ACT_RELU: k_rows_reg<T1, T2, T3, true, ZBP_ACT_RELU><<<grid, RR_WG, 0, s>>>(R); break;
+    case ZBP_ACT_TANH: k_rows_reg<T1, T2, T3, true, ZBP_ACT_TANH><<<grid, RR_WG, 0, s>>>(R); break;
+    case ZBP_ACT_SELU: k_rows_reg<T1, T2, T3, true, ZBP_ACT_SELU><<<grid, RR_WG, 0, s>>>(R); break;
+    case ZBP_ACT_LRELU: k_rows_reg<T1, T2, T3, true, ZBP_ACT_LRELU><<<grid, RR_WG, 0, s>>>(R); break;
+    default:
+      if (norm) k_rows_reg<T1, T2, T3, true, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(R);
+      else k_rows_reg<T1, T2, T3, false, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(R);
+  }
+}
+template <int T1, int T2, int T3>
+void launch_act_reg(int act, bool norm, int grid, hipStream_t s, const ActArgs& A) {
+  switch (act) {
+    case ZBP_ACT_RELU: k_act_reg<T1, T2, T3, true, ZBP_ACT_RELU><<<grid, RR_WG, 0, s>>>(A); break;
+    case ZBP_ACT_TANH: k_act_reg<T1, T2, T3, true, ZBP_ACT_TANH><<<grid, RR_WG, 0, s>>>(A); break;
+    case ZBP_ACT_SELU: k_act_reg<T1, T2, T3, true, ZBP_ACT_SELU><<<grid, RR_WG, 0, s>>>(A); break;
+    case ZBP_ACT_LRELU: k_act_reg<T1, T2, T3, true, ZBP_ACT_LRELU><<<grid, RR_WG, 0, s>>>(A); break;
+    default:
+      if (norm) k_act_reg<T1, T2, T3, true, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(A);
+      else k_act_reg<T1, T2, T3, false, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(A);
+  }
+}
+void launch_act_split(int act, bool norm, int grid, hipStream_t s, const ActArgs& A) {
+  switch (act) {
+    case ZBP_ACT_RELU: k_act_split<8, 8, 8, true, ZBP_ACT_RELU><<<grid, 256, 0, s>>>(A); break;
+    case ZBP_ACT_TANH: k_act_split<8, 8, 8, true, ZBP_ACT_TANH><<<grid, 256, 0, s>>>(A); break;
+    case ZBP_ACT_SELU: k_act_split<8, 8, 8, true, ZBP_ACT_SELU><<<grid, 256, 0, s>>>(A); break;
+    case ZBP_ACT_LRELU: k_act_split<8, 8, 8, true, ZBP_ACT_LRELU><<<grid, 256, 0, s>>>(A); break;
+    default:
+      if (norm) k_act_split<8, 8, 8, true, ZBP_ACT_ELU><<<grid, 256, 0, s>>>(A);
+      else k_act_split<8, 8, 8, false, ZBP_ACT_ELU><<<grid, 256, 0, s>>>(A);
+  }
+}
+
 PackArgs pack_args(const Layout& lo, const zbp_net* a, const zbp_net* c, float* ws) {
   PackArgs P{};
   P.n[0] = lo.n[0];
@@ -1721,21 +1839,20 @@ extern "C" {
 const char* zbp_last_error(void) { return g_err; }
 
 int64_t zbp_workspace_floats(const zbp_net* actor, const zbp_net* critic, int32_t batch) {
-  if (check_net(actor) || check_net(critic) || batch < TR || batch % TR) return -1;
+  if (const char* e = check_nets(actor, critic)) return fail(-1, e);
+  if (batch < TR || batch % TR) return fail(-1, "zbp_workspace_floats: batch must be a positive multiple of 32");
   return make_layout(actor, critic, batch).total;
 }
 
 int zbp_pack(const zbp_net* actor, const zbp_net* critic, float* ws, int32_t batch, void* stream) {
-  if (const char* e = check_net(actor)) return fail(-1, e);
-  if (const char* e = check_net(critic)) return fail(-1, e);
+  if (const char* e = check_nets(actor, critic)) return fail(-1, e);
   if (!ws || batch < TR || batch % TR) return fail(-1, "zbp_pack: workspace / batch");
   return do_pack(make_layout(actor, critic, batch), actor, critic, ws, (hipStream_t)stream);
 }
 
 int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_param, float* std_grad,
                   const zbp_batch* batch, const zbp_loss_cfg* loss, float* ws, float* stats, void* stream) {
-  if (const char* e = check_net(actor)) return fail(-1, e);
-  if (const char* e = check_net(critic)) return fail(-1, e);
+  if (const char* e = check_nets(actor, critic)) return fail(-1, e);
   if (!batch || !loss || !ws || !stats || !std_param || !std_grad) return fail(-1, "zbp_minibatch: null argument");
   const int B = batch->batch;
   if (B < TR || B % TR) return fail(-1, "zbp_minibatch: batch must be a positive multiple of 32");
@@ -1785,14 +1902,10 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   // the register-resident row kernel for the shipped shapes (ZBP_ROWS=lds: the LDS one, for A/Bs)
   const int shape = reg_shape(lo, B);
   const bool norm = batch->actor_norm.mean || batch->critic_norm.mean;
-  if (shape == 1 && norm)
-    k_rows_reg<16, 16, 8, true><<<2 * (B / 64), RR_WG, 0, s>>>(R);
-  else if (shape == 1)
-    k_rows_reg<16, 16, 8, false><<<2 * (B / 64), RR_WG, 0, s>>>(R);
-  else if (shape == 2 && norm)
-    k_rows_reg<8, 8, 8, true><<<2 * (B / 64), RR_WG, 0, s>>>(R);
+  if (shape == 1)
+    launch_rows_reg<16, 16, 8>(actor->activation, norm, 2 * (B / 64), s, R);
   else if (shape == 2)
-    k_rows_reg<8, 8, 8, false><<<2 * (B / 64), RR_WG, 0, s>>>(R);
+    launch_rows_reg<8, 8, 8>(actor->activation, norm, 2 * (B / 64), s, R);
   else
     k_rows<<<B / TR, ROW_THREADS, lds, s>>>(R);
   if (int rc = launch_check("k_rows")) return rc;
@@ -1835,6 +1948,7 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   D.std_grad = std_grad;
   D.stats = stats;
   D.entropy_coef = loss->entropy_coef;
+  D.log_std = loss->log_std;
   D.ws = ws;
   D.part = lo.part;
   D.rstats = lo.stats;
@@ -1848,8 +1962,7 @@ int zbp_optimizer_step(const zbp_params* params, float* lr, const float* stats, 
                        const zbp_net* critic, float* ws, int32_t batch, int32_t norm_from_minibatch, void* stream) {
   if (!params || params->n_params < 1 || params->n_params > ZBP_MAX_PARAMS || !lr || !stats || !acc || !ws)
     return fail(-1, "zbp_optimizer_step: bad argument");
-  if (const char* e = check_net(actor)) return fail(-1, e);
-  if (const char* e = check_net(critic)) return fail(-1, e);
+  if (const char* e = check_nets(actor, critic)) return fail(-1, e);
   hipStream_t s = (hipStream_t)stream;
   const Layout lo = make_layout(actor, critic, batch);
   OptimArgs O{};
@@ -1886,8 +1999,7 @@ int zbp_optimizer_step(const zbp_params* params, float* lr, const float* stats, 
 
 int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param, const zbp_act_io* io, float* ws,
             int32_t batch, void* stream) {
-  if (const char* e = check_net(actor)) return fail(-1, e);
-  if (const char* e = check_net(critic)) return fail(-1, e);
+  if (const char* e = check_nets(actor, critic)) return fail(-1, e);
   if (!io || !ws || !std_param || !io->obs || !io->critic_obs || !io->actions || !io->st_obs ||
       !io->st_critic_obs || !io->st_actions || !io->st_values || !io->st_log_prob || !io->st_mu || !io->st_sigma)
     return fail(-1, "zbp_act: null argument");
@@ -1923,6 +2035,7 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
   A.s_sig = io->st_sigma;
   A.nrm[0] = io->actor_norm;
   A.nrm[1] = io->critic_norm;
+  A.log_std = io->log_std;
   int off = 0;
   for (int l = 0; l < MAXL; ++l) {
     const int p = lo.n[0].p[l] > lo.n[1].p[l] ? lo.n[0].p[l] : lo.n[1].p[l];
@@ -1951,18 +2064,12 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
   const bool split = shape == 2 && !f_reg && (f_split || io->rows <= ZBP_ACT_SPLIT_MAX);
   const bool norm = A.nrm[0].mean || A.nrm[1].mean;
   hipStream_t s = (hipStream_t)stream;
-  if (split && norm)
-    k_act_split<8, 8, 8, true><<<2 * ((io->rows + 15) / 16), 256, 0, s>>>(A);
-  else if (split)
-    k_act_split<8, 8, 8, false><<<2 * ((io->rows + 15) / 16), 256, 0, s>>>(A);
-  else if (shape == 1 && norm)
-    k_act_reg<16, 16, 8, true><<<wgs, RR_WG, 0, s>>>(A);
+  if (split)
+    launch_act_split(actor->activation, norm, 2 * ((io->rows + 15) / 16), s, A);
   else if (shape == 1)
-    k_act_reg<16, 16, 8, false><<<wgs, RR_WG, 0, s>>>(A);
-  else if (shape == 2 && norm)
-    k_act_reg<8, 8, 8, true><<<wgs, RR_WG, 0, s>>>(A);
+    launch_act_reg<16, 16, 8>(actor->activation, norm, wgs, s, A);
   else if (shape == 2)
-    k_act_reg<8, 8, 8, false><<<wgs, RR_WG, 0, s>>>(A);
+    launch_act_reg<8, 8, 8>(actor->activation, norm, wgs, s, A);
   else
     k_act<<<(io->rows + TR - 1) / TR, 256, lds, s>>>(A);
   return launch_check("k_act");

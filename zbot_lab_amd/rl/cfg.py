@@ -12,6 +12,7 @@ from dataclasses import asdict, dataclass, field
 class RslRlPpoActorCriticCfg:
     class_name: str = "ActorCritic"
     init_noise_std: float = 1.0
+    noise_std_type: str = "scalar"  # rsl_rl: "scalar" (the parameter is sigma) or "log" (log sigma)
     actor_hidden_dims: list = field(default_factory=lambda: [128, 128, 128])
     critic_hidden_dims: list = field(default_factory=lambda: [128, 128, 128])
     activation: str = "elu"

@@ -28,7 +28,23 @@ MAXP = 24
 
 class Net(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("dim", C.c_int32 * (MAXL + 1)), ("w", C.c_void_p * MAXL),
-                ("b", C.c_void_p * MAXL), ("gw", C.c_void_p * MAXL), ("gb", C.c_void_p * MAXL)]
+                ("b", C.c_void_p * MAXL), ("gw", C.c_void_p * MAXL), ("gb", C.c_void_p * MAXL),
+                ("activation", C.c_int32)]
+
+
+# zbp_net.activation (ZBP_ACT_*): the rsl_rl activation modules the kernels state, each with torch's
+# default constants only (ELU alpha 1, LeakyReLU slope 0.01; ReLU / Tanh / SELU have none)
+ACTIVATIONS = {nn.ELU: 0, nn.ReLU: 1, nn.Tanh: 2, nn.SELU: 3, nn.LeakyReLU: 4}
+
+
+def activation_code(m: nn.Module):
+    """ZBP_ACT_* of an activation module, or None when the kernels do not state it (another module,
+    or a non-default constant)."""
+    code = ACTIVATIONS.get(type(m))
+    if code is None or (isinstance(m, nn.ELU) and m.alpha != 1.0) or (
+            isinstance(m, nn.LeakyReLU) and m.negative_slope != 0.01):
+        return None
+    return code
 
 
 class ObsNorm(C.Structure):
@@ -47,7 +63,7 @@ class Batch(C.Structure):
 
 class LossCfg(C.Structure):
     _fields_ = [("clip_param", C.c_float), ("value_loss_coef", C.c_float), ("entropy_coef", C.c_float),
-                ("use_clipped_value_loss", C.c_int32)]
+                ("use_clipped_value_loss", C.c_int32), ("log_std", C.c_int32)]
 
 
 class ActIO(C.Structure):
@@ -55,7 +71,8 @@ class ActIO(C.Structure):
                 ("st_obs", C.c_void_p), ("st_critic_obs", C.c_void_p), ("st_actions", C.c_void_p),
                 ("st_values", C.c_void_p), ("st_log_prob", C.c_void_p), ("st_mu", C.c_void_p), ("st_sigma", C.c_void_p),
                 ("rows", C.c_int32), ("obs_dim", C.c_int32), ("critic_obs_dim", C.c_int32), ("num_actions", C.c_int32),
-                ("noise_step", C.c_int32), ("noise_seed", C.c_int32), ("actor_norm", ObsNorm), ("critic_norm", ObsNorm)]
+                ("noise_step", C.c_int32), ("noise_seed", C.c_int32), ("actor_norm", ObsNorm), ("critic_norm", ObsNorm),
+                ("log_std", C.c_int32)]
 
 
 class Params(C.Structure):
@@ -143,24 +160,37 @@ def gae(storage, last_values: torch.Tensor, gamma: float, lam: float, normalize:
 
 
 def mlp_layers(seq: nn.Sequential):
-    """The Linear layers of an rsl_rl MLP, or None when it is not Linear / ELU alternating."""
+    """The Linear layers of an rsl_rl MLP, or None when it is not Linear / activation alternating with
+    one of the kernels' activations (ACTIVATIONS, default constants) throughout."""
     lin = [m for m in seq if isinstance(m, nn.Linear)]
     acts = [m for m in seq if not isinstance(m, nn.Linear)]
-    if len(lin) < 1 or len(lin) > MAXL or len(acts) != len(lin) - 1 or not all(isinstance(a, nn.ELU) and a.alpha == 1.0
-                                                                                 for a in acts):
+    if len(lin) < 1 or len(lin) > MAXL or len(acts) != len(lin) - 1:
+        return None
+    if not all(isinstance(m, nn.Linear) == (i % 2 == 0) for i, m in enumerate(seq)):
+        return None
+    codes = {activation_code(a) for a in acts}
+    if None in codes or len(codes) > 1:
         return None
     return lin
 
 
+def mlp_activation(seq: nn.Sequential) -> int:
+    """ZBP_ACT_* of an MLP that mlp_layers accepts (a net without hidden layers has none: ELU's 0)."""
+    acts = [m for m in seq if not isinstance(m, nn.Linear)]
+    return activation_code(acts[0]) if acts else 0
+
+
 def supported(policy, batch: int) -> bool:
-    """Whether the fused kernels cover this ActorCritic and minibatch size (ELU MLPs, <= 4 layers,
-    inputs <= 32, hidden multiples of 32 up to 256, critic output 1, batch a multiple of 32, fp32 on a
-    GPU)."""
+    """Whether the fused kernels cover this ActorCritic and minibatch size (MLPs of one of the rsl_rl
+    activations, the same for actor and critic, <= 4 layers, inputs <= 32, hidden multiples of 32 up to
+    256, critic output 1, batch a multiple of 32, fp32 on a GPU)."""
     try:
         la, lc = mlp_layers(policy.actor), mlp_layers(policy.critic)
     except TypeError:
         return False
     if la is None or lc is None or batch % 32 or batch < 32 or not available():
+        return False
+    if len(la) > 1 and len(lc) > 1 and mlp_activation(policy.actor) != mlp_activation(policy.critic):
         return False
     if not all(p.is_cuda and p.dtype == torch.float32 for p in policy.parameters()):
         return False
@@ -172,9 +202,10 @@ def supported(policy, batch: int) -> bool:
     return la[-1].out_features <= 13
 
 
-def _net(layers) -> Net:
+def _net(layers, activation: int = 0) -> Net:
     n = Net()
     n.n_layers = len(layers)
+    n.activation = activation
     dims = [layers[0].in_features] + [m.out_features for m in layers]
     for i, d in enumerate(dims):
         n.dim[i] = d
@@ -185,6 +216,12 @@ def _net(layers) -> Net:
         n.w[i], n.b[i] = m.weight.data_ptr(), m.bias.data_ptr()
         n.gw[i], n.gb[i] = m.weight.grad.data_ptr(), m.bias.grad.data_ptr()
     return n
+
+
+def noise_param(policy) -> torch.nn.Parameter:
+    """The policy's action-noise parameter: ``std`` (sigma), or ``log_std`` (log sigma; rsl_rl
+    noise_std_type "log")."""
+    return policy.log_std if getattr(policy, "noise_std_type", "scalar") == "log" else policy.std
 
 
 def obs_norm(module) -> ObsNorm:
@@ -211,22 +248,29 @@ class FusedUpdate:
         self.batch = batch
         pol = alg.policy
         self.la, self.lc = mlp_layers(pol.actor), mlp_layers(pol.critic)
-        if pol.std.grad is None:
-            pol.std.grad = torch.zeros_like(pol.std)
-        self.stats = torch.zeros(4, device=pol.std.device)  # kl mean, value loss, surrogate, entropy
-        self.loss = LossCfg(alg.clip_param, alg.value_loss_coef, alg.entropy_coef, int(alg.use_clipped_value_loss))
+        self.log_std = int(getattr(pol, "noise_std_type", "scalar") == "log")
+        self.noise = noise_param(pol)  # std, or log_std: what the kernels read and write the gradient of
+        if self.noise.grad is None:
+            self.noise.grad = torch.zeros_like(self.noise)
+        self.stats = torch.zeros(4, device=self.noise.device)  # kl mean, value loss, surrogate, entropy
+        self.loss = LossCfg(alg.clip_param, alg.value_loss_coef, alg.entropy_coef, int(alg.use_clipped_value_loss),
+                            self.log_std)
         self._bind()
 
     def _bind(self) -> None:
         """(Re)read every pointer: parameters, .grad buffers, workspace (after a checkpoint load)."""
-        self.na, self.nc = _net(self.la), _net(self.lc)
         pol = self.alg.policy
+        # (a net without hidden layers has no activation module: it takes the other net's code)
+        act = mlp_activation(pol.actor) if len(self.la) > 1 else mlp_activation(pol.critic)
+        self.na, self.nc = _net(self.la, act), _net(self.lc, act)
+        self.noise = noise_param(pol)
         self.norm_a, self.norm_c = obs_norm(pol.actor_obs_normalizer), obs_norm(pol.critic_obs_normalizer)
         n = lib().zbp_workspace_floats(C.byref(self.na), C.byref(self.nc), self.batch)
         if n < 0:
-            raise ZbotError("zbp_workspace_floats: unsupported shapes")
+            msg = lib().zbp_last_error()
+            raise ZbotError(f"zbp_workspace_floats: unsupported nets ({msg.decode() if msg else ''})")
         if getattr(self, "ws", None) is None or self.ws.numel() != n:
-            self.ws = torch.zeros(int(n), device=self.alg.policy.std.device)
+            self.ws = torch.zeros(int(n), device=self.noise.device)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.ws.device).cuda_stream)
@@ -247,8 +291,7 @@ class FusedUpdate:
         b.idx, b.idx_offset, b.batch = indices.data_ptr(), int(offset), self.batch
         b.obs_dim, b.critic_obs_dim, b.num_actions = obs.shape[-1], cobs.shape[-1], storage.actions.shape[-1]
         b.actor_norm, b.critic_norm = self.norm_a, self.norm_c  # (raw storage rows, normalized in the gather)
-        pol = self.alg.policy
-        _check(lib().zbp_minibatch(C.byref(self.na), C.byref(self.nc), _p(pol.std), _p(pol.std.grad), C.byref(b),
+        _check(lib().zbp_minibatch(C.byref(self.na), C.byref(self.nc), _p(self.noise), _p(self.noise.grad), C.byref(b),
                                    C.byref(self.loss), _p(self.ws), _p(self.stats), self._stream()), "zbp_minibatch")
         return self.stats
 
@@ -286,7 +329,7 @@ class FusedUpdate:
 
     def _grads_all_from_minibatch(self) -> bool:
         """The optimizer's parameters are exactly what zbp_minibatch writes gradients for (both nets'
-        weights and biases, the std): then the norm can come from its per-tile sums."""
+        weights and biases, the std or log_std): then the norm can come from its per-tile sums."""
         ps = [p for g in self.alg.optimizer.param_groups for p in g["params"]]
         want = sum(n.dim[l] * n.dim[l + 1] + n.dim[l + 1] for n in (self.na, self.nc) for l in range(n.n_layers))
         return sum(p.numel() for p in ps) == want + int(self.na.dim[self.na.n_layers])
@@ -343,7 +386,8 @@ class FusedUpdate:
         io.st_sigma = storage.sigma[k].data_ptr()
         io.rows, io.obs_dim, io.critic_obs_dim, io.num_actions = n, obs.shape[-1], critic_obs.shape[-1], na
         io.actor_norm, io.critic_norm = self.norm_a, self.norm_c
-        _check(lib().zbp_act(C.byref(self.na), C.byref(self.nc), _p(self.alg.policy.std), C.byref(io), _p(self.ws),
+        io.log_std = self.log_std
+        _check(lib().zbp_act(C.byref(self.na), C.byref(self.nc), _p(self.noise), C.byref(io), _p(self.ws),
                              self.batch, self._stream()), "zbp_act")
         return self._act_out
 

@@ -3,8 +3,9 @@
 ``ppo_learning_notes.md:99-181,417-421,521-548``). rsl_rl itself is not installed in this image, so
 this is a compatible restatement: same module names and tensor semantics, same checkpoint keys.
 
-* ``ActorCritic``: ELU MLPs (actor 23 -> 128x3 -> 6, critic 23 -> 128x3 -> 1), state-independent
-  Gaussian std initialised to ``init_noise_std``.
+* ``ActorCritic``: ELU MLPs (actor 23 -> 128x3 -> 6, critic 23 -> 128x3 -> 1; ``activation`` selects
+  relu / tanh / selu / lrelu instead), state-independent Gaussian std initialised to ``init_noise_std``,
+  held as ``std`` or, with ``noise_std_type="log"``, as ``log_std`` (rsl_rl >= 2.3).
 * ``RolloutStorage``: [T, N] transitions; GAE(gamma, lam) with time-out bootstrapping done in
   ``PPO.process_env_step`` (rewards += gamma * V(s) * time_out), advantages normalised over the
   whole batch.
@@ -91,8 +92,11 @@ class ActorCritic(nn.Module):
     def __init__(self, num_actor_obs: int, num_critic_obs: int, num_actions: int,
                  actor_hidden_dims=(128, 128, 128), critic_hidden_dims=(128, 128, 128),
                  activation: str = "elu", init_noise_std: float = 1.0, actor_obs_normalization: bool = False,
-                 critic_obs_normalization: bool = False, **_):
+                 critic_obs_normalization: bool = False, noise_std_type: str = "scalar", **_):
         super().__init__()
+        if noise_std_type not in ("scalar", "log"):
+            raise ValueError(f"Unknown standard deviation type: {noise_std_type}. Should be 'scalar' or 'log'")
+        self.noise_std_type = noise_std_type
         self.actor = _mlp(num_actor_obs, list(actor_hidden_dims), num_actions, activation)
         self.critic = _mlp(num_critic_obs, list(critic_hidden_dims), 1, activation)
         # rsl_rl 3.x: EmpiricalNormalization in front of a net, or Identity (no state-dict keys, so
@@ -103,14 +107,24 @@ class ActorCritic(nn.Module):
                                      else nn.Identity())
         self.critic_obs_normalizer = (EmpiricalNormalization(num_critic_obs) if critic_obs_normalization
                                       else nn.Identity())
-        self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
+        # rsl_rl: the noise parameter is sigma ("scalar", key `std`) or log sigma ("log", key `log_std`:
+        # sigma = exp(log_std) stays positive whatever the optimizer does)
+        if noise_std_type == "scalar":
+            self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
+        else:
+            self.log_std = nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
         self.distribution: torch.distributions.Normal | None = None
         torch.distributions.Normal.set_default_validate_args(False)
 
     # -- rsl_rl interface
     def update_distribution(self, obs: torch.Tensor) -> None:
         mean = self.actor(self.actor_obs_normalizer(obs))
-        self.distribution = torch.distributions.Normal(mean, mean * 0.0 + self.std)
+        self.distribution = torch.distributions.Normal(mean, mean * 0.0 + self.noise_std)
+
+    @property
+    def noise_std(self) -> torch.Tensor:
+        """The action std per action: ``std``, or ``exp(log_std)``."""
+        return self.std if self.noise_std_type == "scalar" else torch.exp(self.log_std)
 
     def act(self, obs: torch.Tensor) -> torch.Tensor:
         self.update_distribution(obs)

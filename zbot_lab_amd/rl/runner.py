@@ -168,7 +168,7 @@ class OnPolicyRunner:
                    "fps": self.num_steps_per_env * env.num_envs * self.gpu_world_size / (collect_time + learn_time),
                    "mean_reward": statistics.mean(rewbuffer) if rewbuffer else float("nan"),
                    "mean_episode_length": statistics.mean(lenbuffer) if lenbuffer else float("nan"),
-                   "learning_rate": self.alg.learning_rate, "mean_noise_std": self.alg.policy.std.mean().item(),
+                   "learning_rate": self.alg.learning_rate, "mean_noise_std": self.alg.policy.noise_std.mean().item(),
                    **{f"loss/{k}": v for k, v in losses.items()}}
             if self._log_keys:  # rsl_rl: mean over the rollout's per-step extras["log"] values
                 acc = self._log_acc if self._native_acc is None else self._native_acc.index_select(0, self._native_idx)
