@@ -471,6 +471,10 @@ int zb_pair_manifold(const float* pairs, int n, float margin, float* out, void* 
 /* The same with the manifold mode (zb_task_cfg.self_manifold 1..3; zb_pair_manifold = mode 2). */
 int zb_pair_manifold_mode(const float* pairs, int n, float margin, int mode, float* out, void* stream);
 
+/* Privileged critic observations (zb_critic_obs_dim, zb_set_critic_obs_buffer, zb_observe_critic):
+ * device-only entry points without an oracle mirror, declared in their own header. */
+#include "zbot_critic_obs.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--reward_cfg", default=None,
                     help="zbot-6b-walking-v2 reward stage (step0 / step1 / step1_v1 / step1_v2 / step2 / step3 / step4 = v2.py:77-206); the reference "
                          "edits the active reward_cfg in v2.py between its chained 2000-iteration runs")
+    ap.add_argument("--critic_obs", action="store_true", default=False,
+                    help="asymmetric actor-critic: the env also returns the privileged \"critic\" observation group "
+                         "(env cfg critic_observations) and the runner feeds the critic from it")
     ap.add_argument("--env", action="append", default=[], metavar="PATH=VALUE",
                     help="env cfg override by dotted path, e.g. solver.iterations=8 (simulator ablations)")
     return ap
@@ -93,6 +96,8 @@ def main(argv=None) -> dict:
     if args.reward_cfg is not None:
         from zbot_lab_amd.envs.walking_v2 import REWARD_CFGS
         env_cfg.reward_cfg = REWARD_CFGS[args.reward_cfg]
+    if args.critic_obs:
+        env_cfg.critic_observations = True
     zbot_lab_amd.tasks.apply_env_overrides(env_cfg, args.env)
 
     rank, local_rank = 0, 0

@@ -68,6 +68,11 @@ def lib():
     L.zb_gjk_pairs.argtypes = [P, P, C.c_int, C.c_float, P, P]
     L.zb_pair_manifold.argtypes = [P, C.c_int, C.c_float, P, P]
     L.zb_pair_manifold_mode.argtypes = [P, C.c_int, C.c_float, C.c_int, P, P]
+    L.zb_critic_obs_dim.argtypes = [P]
+    L.zb_set_critic_obs_buffer.argtypes = [P, P]
+    L.zb_observe_critic.argtypes = [P, P, P]
+    for name in EXPORTED_CRITIC_OBS:
+        getattr(L, name).restype = C.c_int
     for name in ("zb_create", "zb_num_envs", "zb_reset", "zb_step", "zb_observe", "zb_kernel_variant", "zb_read_log", "zb_set_log_buffers", "zb_set_log_accumulator", "zb_set_done_buffer",
                  "zb_get_state", "zb_set_state", "zb_get_contact_cache", "zb_set_contact_cache", "zb_physics_substeps",
                  "zb_profile_begin", "zb_profile_end", "zb_profile_stride",
@@ -82,6 +87,9 @@ EXPORTED = ["zb_create", "zb_destroy", "zb_last_error", "zb_num_envs", "zb_reset
             "zb_set_contact_cache", "zb_physics_substeps", "zb_profile_begin", "zb_profile_stride",
             "zb_profile_end", "zb_read_stamps", "zb_read_stamps_slowest", "zb_read_stamp_hist", "zb_read_wave_times", "zb_state_dim", "zb_set_link_friction", "zb_set_link_friction_sd",
             "zb_read_curriculum", "zb_gjk_pairs", "zb_pair_manifold", "zb_pair_manifold_mode"]
+
+# include/zbot_critic_obs.h: device-only entry points without an oracle mirror (EXPORTED is zbot.h's own list)
+EXPORTED_CRITIC_OBS = ["zb_critic_obs_dim", "zb_set_critic_obs_buffer", "zb_observe_critic"]
 
 
 def check(rc: int, what: str) -> None:

@@ -3610,15 +3610,23 @@ __global__ void zb_derive_kernel(const zb_model* __restrict__ mg, float4* __rest
   links[DFLT_OFF + 5] = make_float4(f1[0], f1[1], f1[2], 0.f);
 }
 
-__global__ void zb_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
-                                  float* __restrict__ obs) {
+// The observation row of env i's current state, out of line: zb_observe and the critic-observation
+// kernel call the same machine code, so the critic row's policy block is zb_observe's bit for bit
+// (inlined into two kernels the compiler contracted the base quaternion's products differently).
+// o: a global or an LDS row (flat stores).
+__device__ __noinline__ void obs_row(const zb_model* mg, int N, const float* st, int i, float* o) {
   MP m = to_mp(mg);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
   Phys p;
   Mdp d;
   load_state(st, N, i, p, d);
-  write_obs(m, p, d, obs, i);
+  write_obs(m, p, d, o, 0);
+}
+
+__global__ void zb_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
+                                  float* __restrict__ obs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  obs_row(mg, N, st, i, obs + (size_t)i * ZB_OBS_DIM);
 }
 
 template <bool kLinkFriction, bool kTgs, bool kRefresh = false>
@@ -3974,18 +3982,15 @@ __global__ void zb_su_reset_kernel(const zb_model* __restrict__ mg, zb_task_cfg 
 #undef ST
 }
 
-__global__ void zb_su_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
-                                     float* __restrict__ obs) {
+// the observation of env i's current state (standup.py:593-618) into the row o (out of line: obs_row)
+__device__ __noinline__ void su_obs_row(const zb_model* mg, int N, const float* st, int i, float* o) {
   MP m = to_mp(mg);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
   Phys p;
   load_phys(st, N, i, p);
   Kin k;
   fk(m, p, k);
   float bp[3], bq[4];
   link_pose(m, k, 6, bp, bq);
-  float* o = obs + (size_t)i * ZB_SU_OBS_DIM;
   o[0] = bq[0]; o[1] = bq[1]; o[2] = bq[2]; o[3] = bq[3];
 #pragma unroll
   for (int j = 0; j < ND; ++j) {
@@ -3993,6 +3998,13 @@ __global__ void zb_su_observe_kernel(const zb_model* __restrict__ mg, int N, con
     o[10 + j] = p.jqd[j];
     o[16 + j] = st[(size_t)(ZB_SU_ACTIONS + j) * N + i];
   }
+}
+
+__global__ void zb_su_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
+                                     float* __restrict__ obs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  su_obs_row(mg, N, st, i, obs + (size_t)i * ZB_SU_OBS_DIM);
 }
 
 // per-link friction [N][NL] -> state rows ZB_SU_LINK_MU (mu == nullptr: fill with `fill`)
@@ -4450,18 +4462,15 @@ __global__ void zb_v4_reset_kernel(const zb_model* __restrict__ mg, const float4
 #undef ST
 }
 
-__global__ void zb_v4_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
-                                     float* __restrict__ obs) {
+// the observation of env i's current state (v4.py _get_observations) into the row o (out of line: obs_row)
+__device__ __noinline__ void v4_obs_row(const zb_model* mg, int N, const float* st, int i, float* o) {
   MP m = to_mp(mg);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
   Phys p;
   load_phys(st, N, i, p);
   Kin k;
   fk(m, p, k);
   float bp[3], bq[4];
   link_pose(m, k, 6, bp, bq);
-  float* o = obs + (size_t)i * ZB_V4_OBS_DIM;
   o[0] = bq[0]; o[1] = bq[1]; o[2] = bq[2]; o[3] = bq[3];
 #pragma unroll
   for (int j = 0; j < ND; ++j) {
@@ -4473,6 +4482,13 @@ __global__ void zb_v4_observe_kernel(const zb_model* __restrict__ mg, int N, con
   float sn, cs;
   sincos_r(st[(size_t)ZB_V4_TARGET_YAW * N + i] - st[(size_t)ZB_V4_CURRENT_YAW * N + i], &sn, &cs);
   o[23] = atan2f(sn, cs);
+}
+
+__global__ void zb_v4_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
+                                     float* __restrict__ obs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  v4_obs_row(mg, N, st, i, obs + (size_t)i * ZB_V4_OBS_DIM);
 }
 
 // =========================================================================== manager-based env
@@ -4964,13 +4980,9 @@ __global__ void zb_m_reset_kernel(const zb_model* __restrict__ mg, const float4*
 
 // the observation of the current state (reset(): ObservationManager.compute after _reset_idx);
 // noise from this call's stream
-__global__ void zb_m_observe_kernel(const zb_model* __restrict__ mg, zb_task_cfg cfg, int N, const float* __restrict__ st,
-                                    float* __restrict__ obs, const Counters* __restrict__ cnt, uint64_t seed) {
-  MP m = to_mp(mg);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  Phys p;
-  load_phys(st, N, i, p);
+// m_write_obs of env i's current state into the row o (noise stream h; none when cfg.obs_corruption is 0)
+__device__ __forceinline__ void m_observe_row(MP m, const zb_task_cfg& cfg, uint64_t h, const Phys& p,
+                                              const float* __restrict__ st, int N, int i, float* o) {
   Kin k;
   fk(m, p, k);
   float bp[3], bq[4];
@@ -4980,7 +4992,102 @@ __global__ void zb_m_observe_kernel(const zb_model* __restrict__ mg, zb_task_cfg
   float a_obs[ND];
 #pragma unroll
   for (int a = 0; a < ND; ++a) a_obs[a] = st[(size_t)(ZB_M_ACTIONS + a) * N + i];
-  m_write_obs(m, cfg, env_hash(seed, cnt->calls, i), bq, cmd, p, a_obs, obs + (size_t)i * ZB_M_OBS_DIM);
+  m_write_obs(m, cfg, h, bq, cmd, p, a_obs, o);
+}
+
+__global__ void zb_m_observe_kernel(const zb_model* __restrict__ mg, zb_task_cfg cfg, int N, const float* __restrict__ st,
+                                    float* __restrict__ obs, const Counters* __restrict__ cnt, uint64_t seed) {
+  MP m = to_mp(mg);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  Phys p;
+  load_phys(st, N, i, p);
+  m_observe_row(m, cfg, env_hash(seed, cnt->calls, i), p, st, N, i, obs + (size_t)i * ZB_M_OBS_DIM);
+}
+
+// =========================================================================== critic observations
+// The privileged critic row of every env (include/zbot_critic_obs.h; rsl_rl's "critic" observation
+// group): the task's policy observation without corruption, written by the same out-of-line functions
+// as zb_observe, then ZB_CRITIC_TAIL_DIM values the policy is not shown. A launch of its own after the
+// step / finalize launches (zb_set_critic_obs_buffer) or on demand (zb_observe_critic); it reads the
+// state only, so the step kernels do not know about it.
+constexpr int critic_policy_dim(int task) {
+  return task == ZB_TASK_STANDUP_V0 ? ZB_SU_OBS_DIM : task == ZB_TASK_WALKING_V4 ? ZB_V4_OBS_DIM
+         : task == ZB_TASK_MANAGER_V0 ? ZB_M_OBS_DIM : ZB_OBS_DIM;
+}
+static_assert(ZB_M_OBS_DIM + ZB_CRITIC_TAIL_DIM <= ZB_MAX_CRITIC_OBS_DIM && ZB_OBS_DIM + ZB_CRITIC_TAIL_DIM <= ZB_MAX_CRITIC_OBS_DIM &&
+              ZB_V4_OBS_DIM + ZB_CRITIC_TAIL_DIM <= ZB_MAX_CRITIC_OBS_DIM && ZB_SU_OBS_DIM + ZB_CRITIC_TAIL_DIM <= ZB_MAX_CRITIC_OBS_DIM,
+              "critic rows fit the PPO kernels' input limit");
+
+// the tail: base-link velocity in the base frame (3), base height (1), the feet's newest vertical
+// contact force over the robot's weight (2; fz_row < 0: the task keeps no contact sensor, 0), the
+// feet's friction coefficient (1; mu_row < 0: the uniform cfg.friction)
+__device__ __forceinline__ void critic_tail(MP m, const Phys& p, const float* __restrict__ st, int N, int i, int fz_row,
+                                            int mu_row, float friction, float inv_weight, float* o) {
+  Kin k;
+  fk(m, p, k);
+  float V[NB][6];
+  body_vel(k, p, V);
+  // the base link (6, or 5 in the manager task's model: zb_create) sits on composite body 3 either
+  // way, so the body index stays a constant and k / V stay in registers
+  constexpr int b = link_body(6);
+  static_assert(link_body(5) == b, "base link body");
+  float bp[3], bq[4], R[9], w[3], wc[3], lp[3], lr[4];
+  ldc(lp, m->link_pos[m->base_link]);
+  ldc(lr, m->link_rot[m->base_link]);
+  mv3(k.R[b], lp, bp);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) bp[a] += k.p[b][a];
+  qmul(k.q[b], lr, bq);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) w[a] = V[b][a];
+  cross3(w, bp, wc);
+  const float v[3] = {V[b][3] + wc[0], V[b][4] + wc[1], V[b][5] + wc[2]};  // world velocity of the link origin
+  qmat(bq, R);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o[a] = R[a] * v[0] + R[3 + a] * v[1] + R[6 + a] * v[2];  // R^T v
+  o[3] = p.pos[2] + bp[2];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) o[4 + f] = fz_row < 0 ? 0.f : st[(size_t)(fz_row + f) * N + i] * inv_weight;
+  o[6] = mu_row < 0 ? friction
+                    : 0.5f * (st[(size_t)(mu_row + m->foot_links[0]) * N + i] + st[(size_t)(mu_row + m->foot_links[1]) * N + i]);
+}
+
+// One lane per env builds its row in LDS (adjacent lanes read adjacent envs of the [field][N] state);
+// the workgroup's rows are contiguous in the output, so the wave then stores them as one flat run of
+// dwords, 256 B per store instruction. Row stride odd: the row writes and the flat reads spread over
+// the 32 banks. One wave per workgroup spreads 4096 envs over 64 CUs (the kernel is latency-bound).
+constexpr int CRIT_WG = 64;
+template <int kTask>
+__global__ __launch_bounds__(CRIT_WG) void zb_critic_obs_kernel(const zb_model* __restrict__ mg, zb_task_cfg cfg, int N,
+                                                                const float* __restrict__ st, float inv_weight,
+                                                                float* __restrict__ out) {
+  constexpr int PD = critic_policy_dim(kTask), D = PD + ZB_CRITIC_TAIL_DIM, DP = D | 1;
+  __shared__ float rows[CRIT_WG * DP];
+  MP m = to_mp(mg);
+  const int i0 = blockIdx.x * CRIT_WG, i = i0 + (int)threadIdx.x;
+  if (i < N) {
+    float* o = rows + threadIdx.x * DP;
+    Phys p;
+    load_phys(st, N, i, p);
+    if constexpr (kTask == ZB_TASK_WALKING_V2) {
+      obs_row(mg, N, st, i, o);
+      critic_tail(m, p, st, N, i, ZB_S_FEET_FZ_HIST, -1, cfg.friction, inv_weight, o + PD);
+    } else if constexpr (kTask == ZB_TASK_STANDUP_V0) {
+      su_obs_row(mg, N, st, i, o);
+      critic_tail(m, p, st, N, i, -1, ZB_SU_LINK_MU, cfg.friction, inv_weight, o + PD);
+    } else if constexpr (kTask == ZB_TASK_WALKING_V4) {
+      v4_obs_row(mg, N, st, i, o);
+      critic_tail(m, p, st, N, i, ZB_V4_FEET_FZ_HIST, -1, cfg.friction, inv_weight, o + PD);
+    } else {
+      m_observe_row(m, cfg, 0, p, st, N, i, o);  // (the host clears cfg.obs_corruption: no noise draw)
+      critic_tail(m, p, st, N, i, ZB_M_FEET_FZ_HIST, ZB_M_LINK_MU, cfg.friction, inv_weight, o + PD);
+    }
+  }
+  __syncthreads();
+  const int nflat = min(CRIT_WG, N - i0) * D;
+  float* dst = out + (size_t)i0 * D;
+  for (int f = threadIdx.x; f < nflat; f += CRIT_WG) dst[f] = rows[(f / D) * DP + f % D];
 }
 
 // Episode log finalisation, curricula and the full-reset episode_length_buf draw (v2.py:418-422);
@@ -5168,6 +5275,8 @@ struct zb_sim {
   int32_t* u_log_counts = nullptr;
   float* u_log_acc = nullptr;       // optional caller accumulator (zb_set_log_accumulator)
   int64_t* u_done = nullptr;        // optional caller done buffer (zb_set_done_buffer)
+  float* u_critic = nullptr;        // optional caller critic-observation buffer (zb_set_critic_obs_buffer)
+  float inv_weight = 0.f;           // 1 / (total mass x gravity): the critic rows' contact-force scale
   // ZB_DIAG_NO_FINALIZE=1 (diagnostic only, wrong results: no episode log, no full-reset draw, no
   // step counter): zb_step skips the finalize launch, to measure what that launch and its kernel
   // boundary cost per step
@@ -5278,6 +5387,11 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
                  : c->task == ZB_TASK_MANAGER_V0 ? ZB_M_STATE_DIM : ZB_STATE_DIM;
   h->d_cnt = nullptr;
   h->cfg = *c;
+  {
+    double mass = 0.0;
+    for (int b = 0; b < NB; ++b) mass += m->body_mass[b];
+    h->inv_weight = (float)(1.0 / (mass * (double)c->gravity));
+  }
   HIPCHK(hipMalloc(&h->d_model, sizeof(zb_model)), "hipMalloc model");
   HIPCHK(hipMalloc(&h->d_state, sizeof(float) * (size_t)h->state_dim * num_envs), "hipMalloc state");
   HIPCHK(hipMalloc(&h->d_acc, sizeof(float) * ACC_SLOTS * ACC_STRIDE), "hipMalloc acc");
@@ -5546,6 +5660,23 @@ static float log_episode_s(zb_handle h) {
              : 1.f;
 }
 
+// the critic rows of the current state into dst (zb_observe_critic; after every step / reset while a
+// buffer is registered); the manager's policy block without its noise draw
+static int critic_obs(zb_handle h, float* dst, hipStream_t s) {
+  const int blocks = (h->n + CRIT_WG - 1) / CRIT_WG;
+  if (h->task == ZB_TASK_STANDUP_V0)
+    zb_critic_obs_kernel<ZB_TASK_STANDUP_V0><<<blocks, CRIT_WG, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, h->inv_weight, dst);
+  else if (h->task == ZB_TASK_WALKING_V4)
+    zb_critic_obs_kernel<ZB_TASK_WALKING_V4><<<blocks, CRIT_WG, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, h->inv_weight, dst);
+  else if (h->task == ZB_TASK_MANAGER_V0) {
+    zb_task_cfg clean = h->cfg;
+    clean.obs_corruption = 0;
+    zb_critic_obs_kernel<ZB_TASK_MANAGER_V0><<<blocks, CRIT_WG, 0, s>>>(h->d_model, clean, h->n, h->d_state, h->inv_weight, dst);
+  } else
+    zb_critic_obs_kernel<ZB_TASK_WALKING_V2><<<blocks, CRIT_WG, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, h->inv_weight, dst);
+  return launch_check("zb_critic_obs_kernel");
+}
+
 static int finalize(zb_handle h, hipStream_t s, int full, int reset_counts, int is_step, float* obs = nullptr,
                     const uint8_t* term = nullptr, const uint8_t* trunc = nullptr) {
   const int ep_row = h->task == ZB_TASK_STANDUP_V0   ? ZB_SU_EP_LEN
@@ -5582,7 +5713,9 @@ int zb_reset(zb_handle h, const int32_t* env_ids, int n, void* stream) {
     rc = launch_check("zb_wc_fill_kernel");
     if (rc) return rc;
   }
-  return finalize(h, s, env_ids == nullptr || n == h->n, 1, 0);
+  rc = finalize(h, s, env_ids == nullptr || n == h->n, 1, 0);
+  if (rc || !h->u_critic) return rc;
+  return critic_obs(h, h->u_critic, s);
 }
 
 int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
@@ -5629,7 +5762,9 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
   if (prof) ++h->prof_n;
   if (rc) return rc;
   if (h->diag_no_finalize) return 0;  // (diagnostic, DESIGN.md §7: the finalize launch's share of a step)
-  return finalize(h, s, 0, 0, 1, obs, terminated, truncated);
+  rc = finalize(h, s, 0, 0, 1, obs, terminated, truncated);
+  if (rc || !h->u_critic) return rc;
+  return critic_obs(h, h->u_critic, s);
 }
 
 int zb_observe(zb_handle h, float* obs, void* stream) {
@@ -5705,6 +5840,19 @@ int zb_set_done_buffer(zb_handle h, int64_t* dones) {
   if (!h) return set_err(-1, "zb_set_done_buffer", hipSuccess);
   h->u_done = dones;
   return 0;
+}
+
+int zb_critic_obs_dim(zb_handle h) { return h ? critic_policy_dim(h->task) + ZB_CRITIC_TAIL_DIM : -1; }
+
+int zb_set_critic_obs_buffer(zb_handle h, float* buf) {
+  if (!h) return set_err(-1, "zb_set_critic_obs_buffer", hipSuccess);
+  h->u_critic = buf;
+  return 0;
+}
+
+int zb_observe_critic(zb_handle h, float* dst, void* stream) {
+  if (!h || !dst) return set_err(-1, "zb_observe_critic", hipSuccess);
+  return critic_obs(h, dst, (hipStream_t)stream);
 }
 
 int zb_set_log_accumulator(zb_handle h, float* acc) {

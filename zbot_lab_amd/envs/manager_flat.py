@@ -23,7 +23,6 @@ import numpy as np
 import torch
 
 from .. import model as zm
-from .. import spaces
 from .standup_v0 import EventTermCfg
 from .walking_v2 import SimulationCfg, SolverCfg, ZbotDirectEnvV2
 
@@ -211,6 +210,8 @@ class Zbot6BFlatEnvCfg:
     # (the ruling-on-face manifold is compiled into the walking v2 / stand-up kernels only)
     solver: SolverCfg = field(default_factory=lambda: SolverCfg(self_manifold=2))
     seed: int | None = None
+    # privileged critic observations (the "critic" group: the policy terms without noise + 7 state terms)
+    critic_observations: bool = False
 
     # the DirectRLEnv-style fields the shared env base reads
     action_space = 6
@@ -327,8 +328,7 @@ class ZbotManagerBasedRLEnv(ZbotDirectEnvV2):
         cfg = cfg or Zbot6BFlatEnvCfg()
         super().__init__(cfg, render_mode=render_mode, **kwargs)
         self.command_manager = _CommandManager(self)
-        self.single_observation_space = spaces.Dict(policy=spaces.Box(-np.inf, np.inf, (zm.M_OBS_DIM,)))
-        self.observation_space = spaces.Dict(policy=spaces.Box(-np.inf, np.inf, (self.num_envs, zm.M_OBS_DIM)))
+        self._set_observation_spaces(zm.M_OBS_DIM)
 
     def _startup(self) -> None:
         """Startup events: init_my_data (the feet buffers live in the state rows) and

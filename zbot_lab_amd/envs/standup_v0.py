@@ -62,6 +62,7 @@ class Zbot6SUpEnvCfg:
     seed: int | None = None
     reward_cfg: dict = field(default_factory=lambda: {"reward_scales": dict(zm.SU_REWARD_WEIGHTS)})
     curriculum_weights: dict = field(default_factory=lambda: dict(zm.SU_CURRICULUM_WEIGHTS))
+    critic_observations: bool = False  # privileged critic observations (the "critic" group; walking_v2.py)
 
     def task_cfg(self) -> zm.TaskCfg:
         pr = self.events.reset_base.params["pose_range"]

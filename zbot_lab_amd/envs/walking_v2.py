@@ -108,6 +108,9 @@ class ZbotDirectEnvCfgV2:
     solver: SolverCfg = field(default_factory=SolverCfg)
     seed: int | None = None
     reward_cfg: dict = field(default_factory=lambda: {"reward_scales": dict(zm.REWARD_WEIGHTS)})
+    # privileged critic observations (rsl_rl's "critic" group; include/zbot_critic_obs.h): the policy
+    # observation plus base velocity, base height, feet loads and friction, one extra launch per step
+    critic_observations: bool = False
 
     def task_cfg(self) -> zm.TaskCfg:
         unknown = set(self.reward_cfg["reward_scales"]) - set(zm.REWARD_TERMS)
@@ -160,16 +163,33 @@ class ZbotDirectEnvV2:
         self.env_origins = grid_env_origins(self.num_envs, self.cfg.scene.env_spacing).to(self.device)
         # v2.py:250-252 — weights scaled by step_dt (kept as a new dict; the reference mutates cfg)
         self.reward_scales = {k: v * self.step_dt for k, v in self.cfg.reward_cfg["reward_scales"].items()}
-        self.single_observation_space = spaces.Dict(policy=spaces.Box(-np.inf, np.inf, (self.cfg.observation_space,)))
         self.single_action_space = spaces.Box(-np.inf, np.inf, (self.cfg.action_space,))
-        self.observation_space = spaces.Dict(
-            policy=spaces.Box(-np.inf, np.inf, (self.num_envs, self.cfg.observation_space)))
+        # the persistent critic buffer (cfg.critic_observations): the sim refills it after every step / reset
+        self._critic = self.sim.critic_obs_buffer() if getattr(self.cfg, "critic_observations", False) else None
+        self._set_observation_spaces(self.cfg.observation_space)
         self.action_space = spaces.Box(-np.inf, np.inf, (self.num_envs, self.cfg.action_space))
         self.common_step_counter = 0
         self.extras: dict = {}
         self._log_keys = [f"Episode_Reward/{k}" for k in self._task.reward_terms]
         self.obs_buf = None
         self._startup()
+
+    def _set_observation_spaces(self, policy_dim: int) -> None:
+        """The "policy" group, and with cfg.critic_observations the "critic" group and ``state_space``
+        (DirectRLEnv's slot for the critic's input; ``cfg.state_space`` itself stays as configured)."""
+        groups = {"policy": policy_dim}
+        if self._critic is not None:
+            groups["critic"] = self._critic.shape[1]
+        self.single_observation_space = spaces.Dict({k: spaces.Box(-np.inf, np.inf, (d,)) for k, d in groups.items()})
+        self.observation_space = spaces.Dict(
+            {k: spaces.Box(-np.inf, np.inf, (self.num_envs, d)) for k, d in groups.items()})
+        if self._critic is not None:
+            self.single_state_space = self.single_observation_space["critic"]
+            self.state_space = self.observation_space["critic"]
+
+    def _obs(self, policy: torch.Tensor) -> dict:
+        """The observation groups: the critic group is the persistent buffer the step just refilled."""
+        return {"policy": policy} if self._critic is None else {"policy": policy, "critic": self._critic}
 
     def _startup(self) -> None:
         """Startup events (none for v2)."""
@@ -212,7 +232,7 @@ class ZbotDirectEnvV2:
     def reset(self, seed: int | None = None, options: dict | None = None):
         """DirectRLEnv.reset: reset all envs (v2.py:413-459, full-reset episode-length draw)."""
         self.sim.reset(None)
-        self.obs_buf = {"policy": self.sim.observe()}
+        self.obs_buf = self._obs(self.sim.observe())
         self._update_log()
         return self.obs_buf, self.extras
 
@@ -220,7 +240,7 @@ class ZbotDirectEnvV2:
         """DirectRLEnv.step: one fused kernel (physics x decimation, sensor, dones, rewards, resets, obs)."""
         obs, rew, term, trunc = self.sim.step(action)
         self.common_step_counter += 1
-        self.obs_buf = {"policy": obs}
+        self.obs_buf = self._obs(obs)
         self.reward_buf = rew
         self._update_log()
         return self.obs_buf, rew, term, trunc, self.extras
@@ -241,7 +261,7 @@ class ZbotDirectEnvV2:
 
     def get_observations(self):
         if self.obs_buf is None:
-            self.obs_buf = {"policy": self.sim.observe()}
+            self.obs_buf = self._obs(self.sim.observe())
         return self.obs_buf
 
     def render(self, recompute: bool = False):

@@ -64,6 +64,7 @@ class Zbot6SEnvV4Cfg:
     events: EventCfgV4 = field(default_factory=EventCfgV4)
     seed: int | None = None
     reward_cfg: dict = field(default_factory=lambda: {"reward_scales": dict(zm.V4_REWARD_WEIGHTS)})
+    critic_observations: bool = False  # privileged critic observations (the "critic" group; walking_v2.py)
 
     def task_cfg(self) -> zm.TaskCfg:
         pr = self.events.reset_base.params["pose_range"]

@@ -53,6 +53,14 @@ def _policy_obs(obs):
     return obs["policy"] if isinstance(obs, dict) or hasattr(obs, "keys") else obs
 
 
+def _critic_obs(obs):
+    """The privileged "critic" observation group when the env supplies one (rsl_rl's obs_groups), else None:
+    the critic then reads the policy group."""
+    if (isinstance(obs, dict) or hasattr(obs, "keys")) and "critic" in obs.keys():
+        return obs["critic"]
+    return None
+
+
 class OnPolicyRunner:
     def __init__(self, env, train_cfg: dict, log_dir: str | None = None, device: str = "cpu",
                  use_graph: bool | None = None, graph_update: bool | None = None):
@@ -63,19 +71,21 @@ class OnPolicyRunner:
         self._dev_is_cuda = torch.device(device).type == "cuda"
         self.env = env
         self._configure_multi_gpu()
-        obs = _policy_obs(self.env.get_observations())
+        obs_groups = self.env.get_observations()
+        obs, critic = _policy_obs(obs_groups), _critic_obs(obs_groups)
         num_obs = obs.shape[1]
+        num_critic_obs = num_obs if critic is None else critic.shape[1]
         self.alg_cfg.pop("class_name", None)
         self.policy_cfg.pop("class_name", None)
         if train_cfg.get("empirical_normalization"):  # rsl_rl's legacy flag: both normalizers
             warnings.warn("empirical_normalization is deprecated: set the policy's actor_obs_normalization / "
                           "critic_obs_normalization", DeprecationWarning, stacklevel=2)
             self.policy_cfg["actor_obs_normalization"] = self.policy_cfg["critic_obs_normalization"] = True
-        policy = ActorCritic(num_obs, num_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
+        policy = ActorCritic(num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
         self.alg = PPO(policy, device=self.device, multi_gpu_cfg=self.multi_gpu_cfg, **self.alg_cfg)
         self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
         self.save_interval = int(train_cfg["save_interval"])
-        self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, num_obs, num_obs, self.env.num_actions)
+        self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, num_obs, num_critic_obs, self.env.num_actions)
         self.log_dir = log_dir
         self.current_learning_iteration = 0
         self.tot_timesteps = 0
@@ -92,6 +102,9 @@ class OnPolicyRunner:
         self.use_graph = (torch.device(device).type == "cuda" and GRAPHS_SAFE) if use_graph is None else use_graph
         self._graph = None
         self._g_obs = None
+        # the critic group's rows after the latest rollout (None: the critic reads the policy group), and
+        # whether the env hands out one persistent tensor for it (the simulator's registered buffer)
+        self._critic, self._critic_persistent = None, False
         self._update_graph = None
         # the 20 minibatch updates are captured as a second graph after the first (eager) update;
         # PPO.update_steps releases its autograd graph so the capture sees fresh AccumulateGrad
@@ -123,7 +136,10 @@ class OnPolicyRunner:
         env = self.env
         if init_at_random_ep_len:
             env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
-        obs = _policy_obs(env.get_observations()).to(self.device)
+        obs_groups = env.get_observations()
+        obs = _policy_obs(obs_groups).to(self.device)
+        critic = _critic_obs(obs_groups)
+        self._critic = None if critic is None else critic.to(self.device)
         self.alg.policy.train()
         if self.is_distributed:
             self.alg.broadcast_parameters()
@@ -136,7 +152,7 @@ class OnPolicyRunner:
                     self._graph.replay()
                     obs = self._g_obs
                 else:
-                    obs = self._rollout(obs)
+                    obs = self._rollout(obs, self._critic)
                     if self.use_graph:
                         self._capture(obs)
                         obs = self._g_obs
@@ -144,7 +160,7 @@ class OnPolicyRunner:
                     torch.cuda.synchronize(self.device)
                 collect_time = time.perf_counter() - t0
                 t1 = time.perf_counter()
-                self.alg.compute_returns(obs)
+                self.alg.compute_returns(obs if self._critic is None else self._critic)
             self.alg.draw_minibatch_indices()
             if self._update_graph is not None:
                 self._update_graph.replay()
@@ -184,9 +200,14 @@ class OnPolicyRunner:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
         return self.log
 
-    def _rollout(self, obs: torch.Tensor) -> torch.Tensor:
-        """num_steps_per_env env steps into the storage; episode statistics into ep_stats."""
+    def _rollout(self, obs: torch.Tensor, critic_obs: torch.Tensor | None = None) -> torch.Tensor:
+        """num_steps_per_env env steps into the storage; episode statistics into ep_stats. With a critic
+        group (critic_obs, the rows that go with obs) the critic, its normalizer and the storage take those
+        rows; the last step's are left in self._critic for compute_returns."""
         env = self.env
+        asym = critic_obs is not None
+        cobs = critic_obs if asym else obs
+        first = cobs
         self.ep_stats.zero_()
         if self._log_acc is not None:
             self._log_acc.zero_()
@@ -200,25 +221,30 @@ class OnPolicyRunner:
             # the action noise drawn inside zbp_act (ZBOT_KERNEL_NOISE=0: torch.randn, as the torch path)
             kn = os.environ.get("ZBOT_KERNEL_NOISE", "1") != "0"
             for _ in range(self.num_steps_per_env):
-                actions = fr.act(obs, obs, st, kernel_noise=kn)
+                actions = fr.act(obs, cobs, st, kernel_noise=kn)  # (copies both rows into the storage)
                 obs_d, rewards, dones, extras = env.step(actions.to(env.device))
                 obs = _policy_obs(obs_d).to(self.device)
+                cobs = _critic_obs(obs_d).to(self.device) if asym else obs
                 tout = extras.get("time_outs") if isinstance(extras, dict) else None
                 fr.env_post(st, rewards.to(self.device), dones.to(self.device),
                             None if tout is None else tout.to(self.device), self.alg.gamma, self.cur_rew, self.cur_len,
                             self.ep_stats)
-                fr.norm_update(obs, obs)  # (no launch when no normalizer is on)
+                fr.norm_update(obs, cobs)  # (no launch when no normalizer is on)
                 self._accumulate_log(extras)
             self._extras = extras
+            self._end_rollout(first, cobs, asym)
             return obs
         for _ in range(self.num_steps_per_env):
-            actions = self.alg.act(obs, obs)
+            # the critic group may be a persistent buffer that the step below overwrites, and PPO.act keeps
+            # a reference until process_env_step: hand it a snapshot
+            actions = self.alg.act(obs, cobs.clone() if asym else obs)
             obs_d, rewards, dones, extras = env.step(actions.to(env.device))
             obs = _policy_obs(obs_d).to(self.device)
+            cobs = _critic_obs(obs_d).to(self.device) if asym else obs
             rewards, dones = rewards.to(self.device), dones.to(self.device)
             self.alg.process_env_step(rewards, dones, extras)
             # rsl_rl: the normalizers see the post-step observation before the next act
-            self.alg.policy.update_normalization(obs, obs)
+            self.alg.policy.update_normalization(obs, cobs)
             self.cur_rew += rewards
             self.cur_len += 1
             d = dones > 0
@@ -228,7 +254,12 @@ class OnPolicyRunner:
             self.cur_len.masked_fill_(d, 0.0)
             self._accumulate_log(extras)
         self._extras = extras
+        self._end_rollout(first, cobs, asym)
         return obs
+
+    def _end_rollout(self, first: torch.Tensor, last: torch.Tensor, asym: bool) -> None:
+        self._critic = last if asym else None
+        self._critic_persistent = asym and first.data_ptr() == last.data_ptr()
 
     def _accumulate_log(self, extras) -> None:
         """Sum this step's extras["log"] values on the device (rsl_rl appends every step's log and
@@ -302,9 +333,16 @@ class OnPolicyRunner:
         storage_step = self.alg.storage.step
         self.alg.storage.step = 0
         g = torch.cuda.CUDAGraph()
+        # the critic group: the env's persistent buffer is read in place (the captured step kernels refill
+        # it, so every replay's first act sees what the previous replay's last step wrote); a fresh tensor
+        # per step is carried in a static buffer like the policy observation
+        g_critic = self._critic if self._critic is None or self._critic_persistent else self._critic.clone()
         with _blas_workspace_fence(self.device), torch.cuda.graph(g):
-            last = self._rollout(self._g_obs)
+            last = self._rollout(self._g_obs, g_critic)
             self._g_obs.copy_(last)
+            if g_critic is not None and self._critic.data_ptr() != g_critic.data_ptr():
+                g_critic.copy_(self._critic)
+                self._critic = g_critic
         self.alg.storage.step = storage_step
         self._graph = g
 

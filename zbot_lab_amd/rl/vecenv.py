@@ -22,6 +22,14 @@ def _as_obs(obs: dict, num_envs: int):
 
 
 class RslRlVecEnvWrapper:
+    """Observation groups pass through unchanged: ``{"policy": ...}``, plus ``"critic"`` when the env cfg
+    sets ``critic_observations``.
+
+    Two of the returned tensors are persistent buffers that the simulator rewrites in place, not fresh
+    tensors: ``dones`` (zb_set_done_buffer) and the ``"critic"`` group (zb_set_critic_obs_buffer). The next
+    ``step()`` / ``reset()`` overwrites them, so a caller that keeps either across a step must clone it;
+    the runner copies both into its rollout storage before it steps again."""
+
     def __init__(self, env, clip_actions: float | None = None):
         self.env = env
         self.clip_actions = clip_actions

@@ -130,6 +130,26 @@ class ZbotSim:
             nat.check(self.lib.zb_set_done_buffer(self._h, nat.ptr(self._dones)), "zb_set_done_buffer")
         return self._dones
 
+    @property
+    def critic_obs_dim(self) -> int:
+        """Width of the privileged critic row of this task (zb_critic_obs_dim; include/zbot_critic_obs.h)."""
+        return int(self.lib.zb_critic_obs_dim(self._h))
+
+    def critic_obs_buffer(self) -> torch.Tensor:
+        """A persistent float32 [N, critic_obs_dim] tensor that every later step / reset fills with the critic
+        rows of the state it leaves, in a launch of its own after the step's (zb_set_critic_obs_buffer).
+        Registered and filled on first use; the same tensor afterwards, overwritten by the next step."""
+        if getattr(self, "_critic", None) is None:
+            self._critic = self.observe_critic()
+            nat.check(self.lib.zb_set_critic_obs_buffer(self._h, nat.ptr(self._critic)), "zb_set_critic_obs_buffer")
+        return self._critic
+
+    def observe_critic(self) -> torch.Tensor:
+        """The critic rows of the current state, on demand (zb_observe_critic)."""
+        out = torch.empty(self.num_envs, self.critic_obs_dim, dtype=torch.float32, device=self.device)
+        nat.check(self.lib.zb_observe_critic(self._h, nat.ptr(out), _stream(self.device)), "zb_observe_critic")
+        return out
+
     def set_log_accumulator(self, acc: torch.Tensor | None) -> None:
         """Register a device float[ZB_LOG_LEN + ZB_LOG_COUNTS] accumulator that every later step adds the
         log's current values to inside its finalize launch (zb_set_log_accumulator; the PPO runner's
