@@ -25,6 +25,14 @@
 // k_obs_merge (zbp_norm_update). Exact fp32 throughout (the MFMA is a k-ordered fmaf chain);
 // results differ from torch's only by summation order. MI355X mapping: the weights (<= 450 KB per
 // net) stay L2-resident; design and measurements in DESIGN.md §7 (round 5).
+//
+// Every formula is stated once, in a __forceinline__ helper that every kernel computing it calls:
+// sigma_of, logp_term, kl_term, surrogate, gauss_grad, value_loss (beside act_f), sample_action (the act
+// kernels' draw and stores, beside noise_at), rr_input (the register kernels' first-layer operand) and
+// rr_forward_chain / rr_backward_chain (a net's pass in the register kernels). Host side: with_act (the one
+// switch over the activations, device side too), with_act_norm (the register kernels' instantiation set),
+// lds_row_tile (the LDS row tile of k_rows / k_act) and TileMap (the weight tiles, shared by Layout,
+// k_wgrad and k_reduce). DESIGN.md §7, "One statement of each PPO formula".
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -32,6 +40,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "zbot_ppo.h"
 
@@ -46,6 +56,14 @@ constexpr int NSTAT = 16;           // per-row-tile partial sums (surrogate, val
 // C5 nets' 97 KB of activations one workgroup fits a CU, so two waves share each SIMD and cover each
 // other's LDS / L2 waits
 constexpr int ROW_THREADS = 512;
+// zbp_act's kernel choice by rollout rows: the register-resident forward (k_act_reg / k_act_split) from
+// ZBP_ACT_REG_MIN rows, the split-output one (k_act_split, the 128-wide nets) up to ZBP_ACT_SPLIT_MAX
+#ifndef ZBP_ACT_REG_MIN
+#define ZBP_ACT_REG_MIN 4096
+#endif
+#ifndef ZBP_ACT_SPLIT_MAX
+#define ZBP_ACT_SPLIT_MAX 65536
+#endif
 
 thread_local char g_err[256] = "";
 int fail(int code, const char* what) {
@@ -73,16 +91,21 @@ struct NetW {
   int64_t wr[MAXL], wtr[MAXL];           // the same in k_rows_reg's lane order (forward / backward A operands)
   int64_t x[MAXL], dz[MAXL];             // row buffers: X_l [B][p(l)], dZ_l [B][p(l+1)]
 };
-struct Layout {
-  NetW n[2];
-  int64_t stats;  // [tiles][NSTAT] per-row-tile partial sums
-  int64_t part;   // [splits (the largest)][wtiles][PART] weight-gradient partials
+// the weight tiles of both nets and k_wgrad's launch over them (make_layout fills it; k_wgrad and k_reduce
+// get a copy)
+struct TileMap {
   int wtiles, tile0[2 * MAXL + 1];  // weight tiles of (net, layer) in order, prefix counts
   int ngroups, grp0[2 * MAXL + 1];  // k_wgrad workgroups (<= 4 x 4 output x reduction tiles) of (net, layer), prefix counts
   int splits;                       // the largest row split count
   int sp_nl[2 * MAXL];              // row splits of (net, layer) (one count for all, see make_layout)
   int ord[2 * MAXL];                // k_wgrad launch order of the (net, layer)s
   int blk0[2 * MAXL + 1];           // k_wgrad launch: first workgroup of the (net, layer) at order position i
+};
+struct Layout {
+  NetW n[2];
+  int64_t stats;  // [tiles][NSTAT] per-row-tile partial sums
+  int64_t part;   // [splits (the largest)][wtiles][PART] weight-gradient partials
+  TileMap tm;
   int64_t scratch;  // [max(64, wtiles + 1)] gradient sums of squares: k_norm's per block, or k_reduce's per weight tile
   int64_t rng;      // [1] uint32: the draw counter of the in-kernel action noise, advanced by every k_pack
   int64_t total;
@@ -110,6 +133,7 @@ int wgrad_slots() {
 
 Layout make_layout(const zbp_net* a, const zbp_net* c, int B) {
   Layout lo{};
+  TileMap& tm = lo.tm;
   int64_t off = 0;
   auto take = [&](int64_t n) { int64_t o = off; off += (n + 63) & ~int64_t(63); return o; };
   const zbp_net* nets[2] = {a, c};
@@ -127,23 +151,23 @@ Layout make_layout(const zbp_net* a, const zbp_net* c, int B) {
       w.wtr[l] = take((int64_t)w.p[l] * w.p[l + 1]);
       w.x[l] = take((int64_t)B * w.p[l]);
       w.dz[l] = take((int64_t)B * w.p[l + 1]);
-      lo.tile0[k * MAXL + l] = t;
+      tm.tile0[k * MAXL + l] = t;
       t += (w.p[l + 1] / 32) * (w.p[l] / 32);
     }
-    for (int l = w.L; l < MAXL; ++l) lo.tile0[k * MAXL + l] = t;
+    for (int l = w.L; l < MAXL; ++l) tm.tile0[k * MAXL + l] = t;
   }
-  lo.tile0[2 * MAXL] = t;
-  lo.wtiles = t;
+  tm.tile0[2 * MAXL] = t;
+  tm.wtiles = t;
   // weight-gradient workgroups: per (net, layer) groups of up to 4 output tiles (one wave each) x up
   // to 4 reduction tiles
   int g = 0;
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < MAXL; ++l) {
-      lo.grp0[k * MAXL + l] = g;
+      tm.grp0[k * MAXL + l] = g;
       if (l < lo.n[k].L) g += ((lo.n[k].p[l + 1] / 32 + 3) / 4) * ((lo.n[k].p[l] / 32 + 3) / 4);
     }
-  lo.grp0[2 * MAXL] = g;
-  lo.ngroups = g;
+  tm.grp0[2 * MAXL] = g;
+  tm.ngroups = g;
   lo.stats = take((int64_t)(B / 16) * NSTAT);  // (per 32-row tile of k_rows, per 16-row wave of k_rows_reg)
   // row splits of the weight gradients: as many as fill the device's resident k_wgrad workgroups in
   // ONE round (groups x splits <= slots; a second, partly filled round would leave most CUs idle for
@@ -163,13 +187,13 @@ Layout make_layout(const zbp_net* a, const zbp_net* c, int B) {
       const int k = nl / MAXL, l = nl % MAXL;
       const bool busy = l < lo.n[k].L && lo.n[k].p[l + 1] >= 64 && lo.n[k].p[l] >= 64;
       if ((pass == 0) != busy) continue;
-      lo.ord[pos] = nl;
-      lo.blk0[pos++] = b;
-      lo.sp_nl[nl] = s;
-      b += (lo.grp0[nl + 1] - lo.grp0[nl]) * s;
+      tm.ord[pos] = nl;
+      tm.blk0[pos++] = b;
+      tm.sp_nl[nl] = s;
+      b += (tm.grp0[nl + 1] - tm.grp0[nl]) * s;
     }
-  lo.blk0[2 * MAXL] = b;
-  lo.splits = s;
+  tm.blk0[2 * MAXL] = b;
+  tm.splits = s;
   lo.part = take((int64_t)s * t * PART);
   lo.scratch = take(t + 1 > 64 ? t + 1 : 64);
   lo.rng = take(1);
@@ -232,29 +256,72 @@ __device__ __forceinline__ float dact_f(float x) {
   if (kAct == ZBP_ACT_LRELU) return x > 0.f ? 1.f : kLreluSlope;
   return x > 0.f ? 1.f : x + 1.f;  // ELU'(z) = exp(z) = x + 1 for z <= 0
 }
-__device__ __forceinline__ float act_rt(int act, float v) {
+// The one switch over the activations: f(std::integral_constant<int, ZBP_ACT_*>) for a runtime value.
+// The LDS kernels' act_rt / dact_rt and the host's choice of a register-kernel instantiation go through it.
+template <class F>
+__host__ __device__ __forceinline__ auto with_act(int act, F&& f) {
   switch (act) {
-    case ZBP_ACT_RELU: return act_f<ZBP_ACT_RELU>(v);
-    case ZBP_ACT_TANH: return act_f<ZBP_ACT_TANH>(v);
-    case ZBP_ACT_SELU: return act_f<ZBP_ACT_SELU>(v);
-    case ZBP_ACT_LRELU: return act_f<ZBP_ACT_LRELU>(v);
-    default: return act_f<ZBP_ACT_ELU>(v);
+    case ZBP_ACT_RELU: return f(std::integral_constant<int, ZBP_ACT_RELU>{});
+    case ZBP_ACT_TANH: return f(std::integral_constant<int, ZBP_ACT_TANH>{});
+    case ZBP_ACT_SELU: return f(std::integral_constant<int, ZBP_ACT_SELU>{});
+    case ZBP_ACT_LRELU: return f(std::integral_constant<int, ZBP_ACT_LRELU>{});
+    default: return f(std::integral_constant<int, ZBP_ACT_ELU>{});
   }
+}
+__device__ __forceinline__ float act_rt(int act, float v) {
+  return with_act(act, [v](auto a) { return act_f<decltype(a)::value>(v); });
 }
 __device__ __forceinline__ float dact_rt(int act, float x) {
-  switch (act) {
-    case ZBP_ACT_RELU: return dact_f<ZBP_ACT_RELU>(x);
-    case ZBP_ACT_TANH: return dact_f<ZBP_ACT_TANH>(x);
-    case ZBP_ACT_SELU: return dact_f<ZBP_ACT_SELU>(x);
-    case ZBP_ACT_LRELU: return dact_f<ZBP_ACT_LRELU>(x);
-    default: return dact_f<ZBP_ACT_ELU>(x);
-  }
+  return with_act(act, [x](auto a) { return dact_f<decltype(a)::value>(x); });
 }
+
+// ---- the PPO arithmetic, each formula stated once (every row / act kernel calls these; the reductions
+// over actions and rows stay in the kernels)
+constexpr float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
 // the Gaussian's sigma and log sigma of one action from the noise parameter p: sigma itself
 // (zbp_loss_cfg.log_std == 0), or log sigma (rsl_rl noise_std_type "log": sigma = exp(p), log sigma = p)
 __device__ __forceinline__ void sigma_of(float p, int log_std, float& s, float& ls) {
   if (log_std) { s = expf(p); ls = p; }
   else { s = p; ls = logf(p); }
+}
+// one action's term of the Gaussian log-probability, d = action - mu
+__device__ __forceinline__ float logp_term(float d, float s, float ls) { return -(d * d) / (2.f * (s * s)) - ls - kLog2Pi; }
+// one action's term of KL(old || new) as rsl_rl writes it: old (om, os) from the storage, new (mu, s)
+__device__ __forceinline__ float kl_term(float mu, float s, float om, float os) {
+  return logf(s / os + 1e-5f) + (os * os + (om - mu) * (om - mu)) / (2.f * (s * s)) - 0.5f;
+}
+// a row's clipped surrogate max(-adv ratio, -adv clamp(ratio)) and g = dL / dlog_prob of its mean over the batch
+__device__ __forceinline__ void surrogate(float ratio, float adv, float clip, float invB, float& surr, float& g) {
+  const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
+  const float s1 = -adv * ratio, s2 = -adv * rc;
+  surr = fmaxf(s1, s2);
+  // d max(s1, s2) / d ratio (torch.max splits a tie evenly; clamp passes the gradient inside
+  // [1 - clip, 1 + clip], bounds included)
+  const float in = (ratio >= 1.f - clip && ratio <= 1.f + clip) ? 1.f : 0.f;
+  const float w1 = s1 > s2 ? 1.f : (s1 < s2 ? 0.f : 0.5f);
+  g = (w1 * -adv + (1.f - w1) * -adv * in) * ratio * invB;
+}
+// one action's dL / dmu and its row's term of dL / dsigma from g = dL / dlog_prob, diff = action - mu
+__device__ __forceinline__ void gauss_grad(float g, float diff, float s, float& dmu, float& dsig) {
+  dmu = g * diff / (s * s);
+  dsig = g * (diff * diff / (s * s * s) - 1.f / s);
+}
+// a row's value loss (clipped around the stored value tv, or plain) and dv = dL / dvalue of its weighted batch mean
+__device__ __forceinline__ void value_loss(float v, float tv, float ret, const zbp_loss_cfg& lc, float invB, float& vl,
+                                           float& dv) {
+  if (lc.use_clipped_value_loss) {
+    const float clip = lc.clip_param, vd = v - tv;
+    const float vc = tv + fminf(fmaxf(vd, -clip), clip);
+    const float ea = (v - ret) * (v - ret), ec = (vc - ret) * (vc - ret);
+    vl = fmaxf(ea, ec);
+    const float wa = ea > ec ? 1.f : (ea < ec ? 0.f : 0.5f);  // (a tie split evenly, the clamp's bounds included, as above)
+    const float in = (vd >= -clip && vd <= clip) ? 1.f : 0.f;
+    dv = wa * 2.f * (v - ret) + (1.f - wa) * 2.f * (vc - ret) * in;
+  } else {
+    vl = (ret - v) * (ret - v);
+    dv = 2.f * (v - ret);
+  }
+  dv *= lc.value_loss_coef * invB;
 }
 
 // C[32 rows][32 cols] = sum_k A[r][k] B[k][c] over k < kp (kp a multiple of 32): A row-major in LDS
@@ -488,37 +555,26 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
     if (tid < TR) {
       const int i = tid;
       const int64_t row = bt.idx[bt.idx_offset + row0 + i];
-      const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
       float lp = 0.f;
       for (int a = 0; a < NA; ++a) {
         const float mu = lds[A.lds_out + i * 33 + a];
         float s, ls;
         sigma_of(A.std_param[a], A.lc.log_std, s, ls);
-        const float x = bt.actions[row * NA + a], diff = x - mu;
-        lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
-        const float os = bt.sigma[row * NA + a], om = bt.mu[row * NA + a];
-        kl += logf(s / os + 1e-5f) + (os * os + (om - mu) * (om - mu)) / (2.f * (s * s)) - 0.5f;
+        lp += logp_term(bt.actions[row * NA + a] - mu, s, ls);
+        kl += kl_term(mu, s, bt.mu[row * NA + a], bt.sigma[row * NA + a]);
       }
-      const float adv = bt.advantages[row], clip = A.lc.clip_param;
-      const float ratio = expf(lp - bt.log_prob[row]);
-      const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
-      const float s1 = -adv * ratio, s2 = -adv * rc;
-      surr = fmaxf(s1, s2);
-      // d max(s1, s2) / d ratio (torch.max splits a tie evenly; clamp passes the gradient inside
-      // [1 - clip, 1 + clip], bounds included)
-      const float in = (ratio >= 1.f - clip && ratio <= 1.f + clip) ? 1.f : 0.f;
-      const float w1 = s1 > s2 ? 1.f : (s1 < s2 ? 0.f : 0.5f);
-      const float g = (w1 * -adv + (1.f - w1) * -adv * in) * ratio * invB;  // dL / dlog_prob
+      float g;
+      surrogate(expf(lp - bt.log_prob[row]), bt.advantages[row], A.lc.clip_param, invB, surr, g);
       for (int a = 0; a < Pout; ++a) {
         float d = 0.f;
         if (a < NA) {
           const float mu = lds[A.lds_out + i * 33 + a];
-          const float s = A.lc.log_std ? expf(A.std_param[a]) : A.std_param[a];
-          const float diff = bt.actions[row * NA + a] - mu;
-          d = g * diff / (s * s);
+          float s, ls, ds;
+          sigma_of(A.std_param[a], A.lc.log_std, s, ls);
+          gauss_grad(g, bt.actions[row * NA + a] - mu, s, d, ds);
 #pragma unroll
           for (int b = 0; b < NSTAT - 3; ++b)
-            if (b == a) sg[b] = g * (diff * diff / (s * s * s) - 1.f / s);
+            if (b == a) sg[b] = ds;
         }
         dz[i * (Pout + 4) + a] = d;
         A.ws[wa.dz[wa.L - 1] + rbo(Pout, a, row0 + i)] = d;
@@ -551,21 +607,8 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
     if (tid < TR) {
       const int i = tid;
       const int64_t row = bt.idx[bt.idx_offset + row0 + i];
-      const float v = lds[A.lds_out + i * 33], tv = bt.values[row], ret = bt.returns[row], clip = A.lc.clip_param;
       float dv;
-      if (A.lc.use_clipped_value_loss) {
-        const float vd = v - tv;
-        const float vc = tv + fminf(fmaxf(vd, -clip), clip);
-        const float ea = (v - ret) * (v - ret), ec = (vc - ret) * (vc - ret);
-        vl = fmaxf(ea, ec);
-        const float wa_ = ea > ec ? 1.f : (ea < ec ? 0.f : 0.5f);
-        const float in = (vd >= -clip && vd <= clip) ? 1.f : 0.f;
-        dv = wa_ * 2.f * (v - ret) + (1.f - wa_) * 2.f * (vc - ret) * in;
-      } else {
-        vl = (ret - v) * (ret - v);
-        dv = 2.f * (v - ret);
-      }
-      dv *= A.lc.value_loss_coef * invB;
+      value_loss(lds[A.lds_out + i * 33], bt.values[row], bt.returns[row], A.lc, invB, vl, dv);
       for (int a = 0; a < Pout; ++a) {
         dz[i * (Pout + 4) + a] = a == 0 ? dv : 0.f;
         A.ws[wc.dz[wc.L - 1] + rbo(Pout, a, row0 + i)] = a == 0 ? dv : 0.f;
@@ -733,22 +776,30 @@ __device__ __forceinline__ void rr_backward(const NetW& w, int l, float* __restr
 // the tile's input rows (through the permutation) as the first layer's B operand, zero-padded to 32
 // (kNorm: normalized when the net has a normalizer; the register kernels are instantiated without it
 // for nets that have none, so those keep their code and register budget)
+// x[o][u] = feature 16 o + 4 g + u of the input row sr (ok: the row exists), normalized; st != nullptr
+// (the rollout's storage slot) gets the row as read
+template <bool kNorm>
+__device__ __forceinline__ void rr_input(const float* sr, int dim, const zbp_obs_norm& nr, bool ok, Tile (&x)[2], float* st) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = 16 * (j >> 2) + 4 * rr_g() + (j & 3);
+    const bool in = ok && k < dim;
+    const float v = in ? sr[k] : 0.f;
+    x[j >> 2][j & 3] = (kNorm && nr.mean && in) ? obs_normalize(nr, k, v) : v;
+    if (st && in) st[k] = v;
+  }
+}
+// (the minibatch: the row through the permutation; X_0, normalized, also to its row buffer)
 template <bool kNorm>
 __device__ __forceinline__ void rr_gather(const NetW& w, float* __restrict__ ws, int row0, const float* src, int dim,
                                           const zbp_obs_norm& nr, int64_t row, Tile (&x)[2]) {
   const int lo = rr_lane_off(32);
   float* xb = rr_base(ws + w.x[0], 32, row0);
-  const float* sr = src + row * dim;
+  rr_input<kNorm>(src + row * dim, dim, nr, true, x, nullptr);
 #pragma unroll
   for (int o = 0; o < 2; ++o)
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = 16 * o + 4 * rr_g() + u;
-      float v = k < dim ? sr[k] : 0.f;
-      if (kNorm && nr.mean && k < dim) v = obs_normalize(nr, k, v);
-      x[o][u] = v;
-      rr_at(xb, o, u)[lo] = v;
-    }
+    for (int u = 0; u < 4; ++u) rr_at(xb, o, u)[lo] = x[o][u];
 }
 
 __device__ __forceinline__ void rr_store_dz(const NetW& w, float* __restrict__ ws, int row0, const Tile (&d)[2]) {
@@ -770,6 +821,28 @@ __device__ __forceinline__ float rr_row_sum(float v) {
 __device__ __forceinline__ float rr_feat_sum(float v) {
   v += __shfl_xor(v, 16);
   return v + __shfl_xor(v, 32);
+}
+
+// one net's forward, x0 -> z (the output layer's pre-activations). Every layer fetches the next layer's
+// first weight chunk before its epilogue; the last one fetches `next`, the backward's first image, in
+// the minibatch pass (kStore: X_l also to HBM) and nothing in the rollout's
+template <int T1, int T2, int T3, bool kStore, int CB, int kAct>
+__device__ __forceinline__ void rr_forward_chain(const NetW& w, float* __restrict__ ws, float4* __restrict__ wl, int row0,
+                                                 const Tile (&x0)[2], Tile (&z)[2], RrStage<CB>& st, const float* next) {
+  Tile x1[T1], x2[T2], x3[T3];
+  rr_forward<2, T1, false, kStore, T1 * T2, CB, kAct>(w, 0, ws, wl, row0, x0, x1, st, ws + w.wr[1]);
+  rr_forward<T1, T2, false, kStore, T2 * T3, CB, kAct>(w, 1, ws, wl, row0, x1, x2, st, ws + w.wr[2]);
+  rr_forward<T2, T3, false, kStore, T3 * 2, CB, kAct>(w, 2, ws, wl, row0, x2, x3, st, ws + w.wr[3]);
+  rr_forward<T3, 2, true, kStore, kStore ? 2 * T3 : 0, CB, kAct>(w, 3, ws, wl, row0, x3, z, st, next);
+}
+// one net's backward from the output layer's dZ (st holds chunk 0 of W_3^T's image on entry)
+template <int T1, int T2, int T3, int CB, int kAct>
+__device__ __forceinline__ void rr_backward_chain(const NetW& w, float* __restrict__ ws, float4* __restrict__ wl, int row0,
+                                                  const Tile (&dz)[2], RrStage<CB>& st) {
+  Tile d3[T3], d2[T2], d1[T1];
+  rr_backward<2, T3, T3 * T2, CB, kAct>(w, 3, ws, wl, row0, dz, d3, st, ws + w.wtr[2]);
+  rr_backward<T3, T2, T2 * T1, CB, kAct>(w, 2, ws, wl, row0, d3, d2, st, ws + w.wtr[1]);
+  rr_backward<T2, T1, 0, CB, kAct>(w, 1, ws, wl, row0, d2, d1, st, nullptr);
 }
 
 constexpr int RR_TR = 16;  // rows per wave
@@ -807,57 +880,38 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   }
 
   // ---- actor: forward, Gaussian log-prob, clipped surrogate, KL; dL/dmu into dZ of the output
-  // (every layer fetches the next layer's first weight chunk before its epilogue; the last forward
-  // layer fetches the backward's)
   rr_fetch<2 * T1, CB>(ws + wa.wr[0], 0, wst);
   {
-    Tile x0[2], x1[T1], x2[T2], x3[T3];
+    Tile x0[2];
     rr_gather<kNorm>(wa, ws, row0, bt.obs, bt.obs_dim, bt.actor_norm, row, x0);
-    rr_forward<2, T1, false, true, T1 * T2, CB, kAct>(wa, 0, ws, wl, row0, x0, x1, wst, ws + wa.wr[1]);
-    rr_forward<T1, T2, false, true, T2 * T3, CB, kAct>(wa, 1, ws, wl, row0, x1, x2, wst, ws + wa.wr[2]);
-    rr_forward<T2, T3, false, true, T3 * 2, CB, kAct>(wa, 2, ws, wl, row0, x2, x3, wst, ws + wa.wr[3]);
-    rr_forward<T3, 2, true, true, 2 * T3, CB, kAct>(wa, 3, ws, wl, row0, x3, z, wst, ws + wa.wtr[3]);
+    rr_forward_chain<T1, T2, T3, true, CB, kAct>(wa, ws, wl, row0, x0, z, wst, ws + wa.wtr[3]);
   }
   {
     // lane (r, g) holds actions 4 g + u (tile 0) and 16 + 4 g + u (tile 1) of row r
-    const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
-    float lp = 0.f, kl = 0.f, diff[8];
+    float lp = 0.f, kl = 0.f, diff[8], sig[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int n = 16 * (j >> 2) + 4 * gq + (j & 3);
       diff[j] = 0.f;
+      sig[j] = 1.f;
       if (n < NA) {
         const float mu = z[j >> 2][j & 3];
-        float s, ls;
-        sigma_of(A.std_param[n], A.lc.log_std, s, ls);
-        const float d = act_in[j & 3] - mu;  // (n < NA only in tile 0: j < 4)
-        diff[j] = d;
-        lp += -(d * d) / (2.f * (s * s)) - ls - kLog2Pi;
-        const float os = sig_in[j & 3], om = mu_in[j & 3];
-        kl += logf(s / os + 1e-5f) + (os * os + (om - mu) * (om - mu)) / (2.f * (s * s)) - 0.5f;
+        float ls;
+        sigma_of(A.std_param[n], A.lc.log_std, sig[j], ls);
+        diff[j] = act_in[j & 3] - mu;  // (n < NA only in tile 0: j < 4)
+        lp += logp_term(diff[j], sig[j], ls);
+        kl += kl_term(mu, sig[j], mu_in[j & 3], sig_in[j & 3]);
       }
     }
     lp = rr_feat_sum(lp);
     kl = rr_feat_sum(kl);
-    const float adv = adv_in, clip = A.lc.clip_param;
-    const float ratio = expf(lp - lp_in);
-    const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
-    const float s1 = -adv * ratio, s2 = -adv * rc;
-    const float surr = fmaxf(s1, s2);
-    // d max(s1, s2) / d ratio (torch.max splits a tie evenly; clamp passes the gradient inside
-    // [1 - clip, 1 + clip], bounds included)
-    const float in = (ratio >= 1.f - clip && ratio <= 1.f + clip) ? 1.f : 0.f;
-    const float w1 = s1 > s2 ? 1.f : (s1 < s2 ? 0.f : 0.5f);
-    const float g = (w1 * -adv + (1.f - w1) * -adv * in) * ratio * invB;  // dL / dlog_prob
+    float surr, g;
+    surrogate(expf(lp - lp_in), adv_in, A.lc.clip_param, invB, surr, g);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int n = 16 * (j >> 2) + 4 * gq + (j & 3);
       float d = 0.f, sg = 0.f;
-      if (n < NA) {
-        const float s = A.lc.log_std ? expf(A.std_param[n]) : A.std_param[n];
-        d = g * diff[j] / (s * s);
-        sg = g * (diff[j] * diff[j] / (s * s * s) - 1.f / s);
-      }
+      if (n < NA) gauss_grad(g, diff[j], sig[j], d, sg);
       dz[j >> 2][j & 3] = d;
       sg = rr_row_sum(sg);  // the std gradient summed over the tile's rows
       if (r == 0 && n < NA) st[3 + n] = sg;
@@ -870,60 +924,34 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
       for (int a = 3 + NA; a < NSTAT; ++a) st[a] = 0.f;
     }
   }
-  {
-    Tile d3[T3], d2[T2], d1[T1];
-    rr_backward<2, T3, T3 * T2, CB, kAct>(wa, 3, ws, wl, row0, dz, d3, wst, ws + wa.wtr[2]);
-    rr_backward<T3, T2, T2 * T1, CB, kAct>(wa, 2, ws, wl, row0, d3, d2, wst, ws + wa.wtr[1]);
-    rr_backward<T2, T1, 0, CB, kAct>(wa, 1, ws, wl, row0, d2, d1, wst, nullptr);
-  }
+  rr_backward_chain<T1, T2, T3, CB, kAct>(wa, ws, wl, row0, dz, wst);
   } else {
   const float tv_in = bt.values[row], ret_in = bt.returns[row];
   // ---- critic: forward, clipped value loss, backward
   rr_fetch<2 * T1, CB>(ws + wc.wr[0], 0, wst);
   {
-    Tile x0[2], x1[T1], x2[T2], x3[T3];
+    Tile x0[2];
     rr_gather<kNorm>(wc, ws, row0, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, row, x0);
-    rr_forward<2, T1, false, true, T1 * T2, CB, kAct>(wc, 0, ws, wl, row0, x0, x1, wst, ws + wc.wr[1]);
-    rr_forward<T1, T2, false, true, T2 * T3, CB, kAct>(wc, 1, ws, wl, row0, x1, x2, wst, ws + wc.wr[2]);
-    rr_forward<T2, T3, false, true, T3 * 2, CB, kAct>(wc, 2, ws, wl, row0, x2, x3, wst, ws + wc.wr[3]);
-    rr_forward<T3, 2, true, true, 2 * T3, CB, kAct>(wc, 3, ws, wl, row0, x3, z, wst, ws + wc.wtr[3]);
+    rr_forward_chain<T1, T2, T3, true, CB, kAct>(wc, ws, wl, row0, x0, z, wst, ws + wc.wtr[3]);
   }
   {
-    const float v = __shfl(z[0][0], r), tv = tv_in, ret = ret_in, clip = A.lc.clip_param;
     float vl, dv;
-    if (A.lc.use_clipped_value_loss) {
-      const float vd = v - tv;
-      const float vc = tv + fminf(fmaxf(vd, -clip), clip);
-      const float ea = (v - ret) * (v - ret), ec = (vc - ret) * (vc - ret);
-      vl = fmaxf(ea, ec);
-      const float wa_ = ea > ec ? 1.f : (ea < ec ? 0.f : 0.5f);
-      const float in = (vd >= -clip && vd <= clip) ? 1.f : 0.f;
-      dv = wa_ * 2.f * (v - ret) + (1.f - wa_) * 2.f * (vc - ret) * in;
-    } else {
-      vl = (ret - v) * (ret - v);
-      dv = 2.f * (v - ret);
-    }
-    dv *= A.lc.value_loss_coef * invB;
+    value_loss(__shfl(z[0][0], r), tv_in, ret_in, A.lc, invB, vl, dv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) dz[j >> 2][j & 3] = (gq == 0 && j == 0) ? dv : 0.f;
     rr_store_dz(wc, ws, row0, dz);
     const float vs = wave_sum(gq == 0 ? vl : 0.f);
     if (lane == 0) st[1] = vs;
   }
-  {
-    Tile d3[T3], d2[T2], d1[T1];
-    rr_backward<2, T3, T3 * T2, CB, kAct>(wc, 3, ws, wl, row0, dz, d3, wst, ws + wc.wtr[2]);
-    rr_backward<T3, T2, T2 * T1, CB, kAct>(wc, 2, ws, wl, row0, d3, d2, wst, ws + wc.wtr[1]);
-    rr_backward<T2, T1, 0, CB, kAct>(wc, 1, ws, wl, row0, d2, d1, wst, nullptr);
-  }
+  rr_backward_chain<T1, T2, T3, CB, kAct>(wc, ws, wl, row0, dz, wst);
   }
 }
 
 // ------------------------------------------------------------------------------- k_wgrad
 struct WgradArgs {
   NetW n[2];
-  int tile0[2 * MAXL + 1], grp0[2 * MAXL + 1], blk0[2 * MAXL + 1], sp_nl[2 * MAXL], ord[2 * MAXL];
-  int wtiles, ngroups, splits, batch;
+  TileMap tm;
+  int batch;
   float* ws;
   int64_t part;
 };
@@ -942,16 +970,17 @@ __global__ __launch_bounds__(256, 2) void k_wgrad(WgradArgs A) {
   __shared__ float4 lds4[2 * WG_CHUNK_F / 4];
   float* lds = reinterpret_cast<float*>(lds4);
   // workgroup -> (net, layer) by the launch prefix, then (group, split) inside it, groups interleaved
+  const TileMap& M = A.tm;
   int pos = 0;
-  while (pos + 1 < 2 * MAXL && A.blk0[pos + 1] <= (int)blockIdx.x) ++pos;
-  const int nl = A.ord[pos];
-  const int ng = A.grp0[nl + 1] - A.grp0[nl], local = (int)blockIdx.x - A.blk0[pos];
-  const int grp = A.grp0[nl] + local % ng, split = local / ng, nsplit = A.sp_nl[nl];
+  while (pos + 1 < 2 * MAXL && M.blk0[pos + 1] <= (int)blockIdx.x) ++pos;
+  const int nl = M.ord[pos];
+  const int ng = M.grp0[nl + 1] - M.grp0[nl], local = (int)blockIdx.x - M.blk0[pos];
+  const int grp = M.grp0[nl] + local % ng, split = local / ng, nsplit = M.sp_nl[nl];
   const NetW& w = A.n[nl / MAXL];
   const int l = nl % MAXL;
   const int P0 = w.p[l], P1 = w.p[l + 1], Tk = P0 / 32, Tn = P1 / 32, KG = (Tk + 3) / 4;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63, c = lane & 31, h = lane >> 5;
-  const int g = grp - A.grp0[nl], nt0 = 4 * (g / KG), kt0 = 4 * (g % KG);
+  const int g = grp - M.grp0[nl], nt0 = 4 * (g / KG), kt0 = 4 * (g % KG);
   const int nb = min(4, Tn - nt0), kb = min(4, Tk - kt0);  // tiles of the block
   const int C = A.batch / 32;  // the split's chunks [c0, c1)
   const int c0 = (int)((int64_t)split * C / nsplit), c1 = (int)((int64_t)(split + 1) * C / nsplit);
@@ -1042,7 +1071,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad(WgradArgs A) {
     for (int b = 0; b < 2; ++b)
       if (on[a][b]) {
         const int nt = nt0 + qn + a, kt = kt0 + qk + b;
-        float* out = A.ws + A.part + ((int64_t)split * A.wtiles + A.tile0[nl] + nt * Tk + kt) * PART;
+        float* out = A.ws + A.part + ((int64_t)split * M.wtiles + M.tile0[nl] + nt * Tk + kt) * PART;
 #pragma unroll
         for (int r = 0; r < 16; ++r) out[acc_row(r) * 32 + acc_col()] = acc[a][b][r];  // [n][k]
         if (kt == 0 && h == 0) out[1024 + c] = bs;
@@ -1053,9 +1082,8 @@ __global__ __launch_bounds__(256, 2) void k_wgrad(WgradArgs A) {
 // ------------------------------------------------------------------------------- k_reduce
 struct ReduceArgs {
   NetW n[2];
-  int tile0[2 * MAXL + 1];
-  int wtiles, splits, row_tiles, batch, num_actions;
-  int sp_nl[2 * MAXL];
+  TileMap tm;
+  int row_tiles, batch, num_actions;
   float* gw[2][MAXL];
   float* gb[2][MAXL];
   const float* std_param;
@@ -1073,7 +1101,7 @@ struct ReduceArgs {
 // (with 256 threads and 8 in flight the launch waited on ~30 dependent rounds of partial loads)
 constexpr int RED_THREADS = 1024;
 __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
-  if (blockIdx.x == (unsigned)A.wtiles) {
+  if (blockIdx.x == (unsigned)A.tm.wtiles) {
     // per-row-tile sums -> stats, the std gradient (+ the entropy bonus term): thread t < 256 sums row
     // tiles t, t + 256, ... (one row = 16 floats = four float4, two rows in flight), then a fixed-order
     // tree over those 256 (deterministic); the other threads only take part in the barriers
@@ -1117,7 +1145,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
       float ent = 0.f;
       // (log std: the parameter is log sigma)
       for (int a = 0; a < A.num_actions; ++a)
-        ent += 0.5f + 0.91893853320467274178f + (A.log_std ? A.std_param[a] : logf(A.std_param[a]));
+        ent += 0.5f + kLog2Pi + (A.log_std ? A.std_param[a] : logf(A.std_param[a]));
       A.stats[0] = tot[2] * invB;  // kl mean
       A.stats[1] = tot[1] * invB;  // value loss
       A.stats[2] = tot[0] * invB;  // surrogate loss
@@ -1131,16 +1159,16 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
         A.std_grad[a] = g;
         ss += g * g;
       }
-      A.norm2[A.wtiles] = ss;
+      A.norm2[A.tm.wtiles] = ss;
     }
     return;
   }
   const int tile = blockIdx.x;
   int nl = 0;
-  while (nl + 1 < 2 * MAXL && A.tile0[nl + 1] <= tile) ++nl;
+  while (nl + 1 < 2 * MAXL && A.tm.tile0[nl + 1] <= tile) ++nl;
   const int net = nl / MAXL, l = nl % MAXL;
   const NetW& w = A.n[net];
-  const int t = tile - A.tile0[nl], kt = w.p[l] / 32;
+  const int t = tile - A.tm.tile0[nl], kt = w.p[l] / 32;
   const int n0 = 32 * (t / kt), k0 = 32 * (t % kt);
   const int D0 = w.d[l], D1 = w.d[l + 1];
   float ss = 0.f;
@@ -1151,8 +1179,8 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
     for (int u = 0; u < 16; ++u) sv[u] = 0.f;
     int sp = 0;
     const float* src = A.ws + A.part + (int64_t)tile * PART + e;
-    const int64_t stride = (int64_t)A.wtiles * PART;
-    const int nsp = A.sp_nl[nl];  // (this tile's layer's splits)
+    const int64_t stride = (int64_t)A.tm.wtiles * PART;
+    const int nsp = A.tm.sp_nl[nl];  // (this tile's layer's splits)
     for (; sp + 16 <= nsp; sp += 16)
 #pragma unroll
       for (int u = 0; u < 16; ++u) sv[u] += src[(int64_t)(sp + u) * stride];
@@ -1290,6 +1318,18 @@ __device__ __forceinline__ float noise_at(const ActArgs& A, int row, int n) {
   const float u2 = (float)(uint32_t)((h >> 16) & 0xFFFFFFu) * 5.9604644775390625e-8f;  // [0, 1)
   return sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
+// action n of `row` from the actor's mean: draws a = mu + sigma * noise, writes the transition's four
+// per-action fields (the action also into the env's input) and returns the action's log-prob term
+__device__ __forceinline__ float sample_action(const ActArgs& A, int64_t row, int n, float mu) {
+  float s, ls;
+  sigma_of(A.std_param[n], A.log_std, s, ls);
+  const float x = mu + s * noise_at(A, row, n), diff = x - mu;
+  A.actions[row * A.na + n] = x;
+  A.s_act[row * A.na + n] = x;
+  A.s_mu[row * A.na + n] = mu;
+  A.s_sig[row * A.na + n] = s;
+  return logp_term(diff, s, ls);
+}
 
 // (the storage slot gets the raw observation, the net the normalized one)
 __device__ void act_gather(const NetW& w, const float* src, int dim, const zbp_obs_norm& nr, float* st, int rows,
@@ -1312,19 +1352,8 @@ __global__ __launch_bounds__(256) void k_act(ActArgs A) {
   net_forward_t<false>(A.n[0], A.ws, 0, A.lds_x, A.lds_out, lds, row0);
   if (tid < TR && row0 + tid < A.rows) {
     const int64_t row = row0 + tid;
-    const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
     float lp = 0.f;
-    for (int a = 0; a < A.na; ++a) {
-      const float mu = lds[A.lds_out + tid * 33 + a];
-      float s, ls;
-      sigma_of(A.std_param[a], A.log_std, s, ls);
-      const float x = mu + s * noise_at(A, row, a), diff = x - mu;
-      lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
-      A.actions[row * A.na + a] = x;
-      A.s_act[row * A.na + a] = x;
-      A.s_mu[row * A.na + a] = mu;
-      A.s_sig[row * A.na + a] = s;
-    }
+    for (int a = 0; a < A.na; ++a) lp += sample_action(A, row, a, lds[A.lds_out + tid * 33 + a]);
     A.s_lp[row] = lp;
   }
   __syncthreads();  // (the output tile is reused by the critic)
@@ -1333,15 +1362,18 @@ __global__ __launch_bounds__(256) void k_act(ActArgs A) {
   if (tid < TR && row0 + tid < A.rows) A.s_val[row0 + tid] = lds[A.lds_out + tid * 33];
 }
 
+// the register act kernels' input: `row` of the net's observations as the first layer's B operand
+// (normalized), the raw row into the storage slot (store: by one wave of the row's workgroup)
+template <bool kNorm>
+__device__ __forceinline__ void act_rr_gather(const ActArgs& A, int net, int64_t row, bool ok, bool store, Tile (&x0)[2]) {
+  const int dim = net ? A.cobs_dim : A.obs_dim;
+  float* st = (net ? A.s_cobs : A.s_obs) + row * dim;
+  rr_input<kNorm>((net ? A.cobs : A.obs) + row * dim, dim, A.nrm[net], ok, x0, store ? st : nullptr);
+}
+
 // k_act on the register-resident forward (k_rows_reg's shapes): one wave per 16 rows, the weights
 // shared through LDS
 template <int T1, int T2, int T3, bool kNorm, int kAct>
-#ifndef ZBP_ACT_REG_MIN
-#define ZBP_ACT_REG_MIN 4096
-#endif
-#ifndef ZBP_ACT_SPLIT_MAX
-#define ZBP_ACT_SPLIT_MAX 65536
-#endif
 __global__ __launch_bounds__(RR_WG, 2) void k_act_reg(ActArgs A) {
   constexpr int CB = 32;
   __shared__ float4 wl[2 * CB * 64];
@@ -1351,45 +1383,20 @@ __global__ __launch_bounds__(RR_WG, 2) void k_act_reg(ActArgs A) {
   const int row0 = ((blockIdx.x >> 1) * (RR_WG / 64) + (threadIdx.x >> 6)) * RR_TR;  // (waves past the rows run on zeros, store nothing)
   const int64_t row = row0 + r;
   const bool ok = row < A.rows;
-  const int na = A.na;
   Tile z[2];
   RrStage<CB> wst;
   rr_fetch<2 * T1, CB>(A.ws + A.n[net].wr[0], 0, wst);
   {
-    const NetW& w = A.n[net];
-    const int dim = net ? A.cobs_dim : A.obs_dim;
-    const float* src = (net ? A.cobs : A.obs) + row * dim;
-    float* st = (net ? A.s_cobs : A.s_obs) + row * dim;
-    Tile x0[2], x1[T1], x2[T2], x3[T3];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = 16 * (j >> 2) + 4 * gq + (j & 3);
-      const float v = (ok && k < dim) ? src[k] : 0.f;
-      x0[j >> 2][j & 3] = (kNorm && A.nrm[net].mean && ok && k < dim) ? obs_normalize(A.nrm[net], k, v) : v;
-      if (ok && k < dim) st[k] = v;
-    }
-    rr_forward<2, T1, false, false, T1 * T2, CB, kAct>(w, 0, A.ws, wl, 0, x0, x1, wst, A.ws + w.wr[1]);
-    rr_forward<T1, T2, false, false, T2 * T3, CB, kAct>(w, 1, A.ws, wl, 0, x1, x2, wst, A.ws + w.wr[2]);
-    rr_forward<T2, T3, false, false, T3 * 2, CB, kAct>(w, 2, A.ws, wl, 0, x2, x3, wst, A.ws + w.wr[3]);
-    rr_forward<T3, 2, true, false, 0, CB, kAct>(w, 3, A.ws, wl, 0, x3, z, wst, nullptr);
+    Tile x0[2];
+    act_rr_gather<kNorm>(A, net, row, ok, true, x0);
+    rr_forward_chain<T1, T2, T3, false, CB, kAct>(A.n[net], A.ws, wl, 0, x0, z, wst, nullptr);
     if (net == 0) {
       // lane (r, g) holds actions 4 g + u and 16 + 4 g + u of row r
-      const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
       float lp = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int n = 16 * (j >> 2) + 4 * gq + (j & 3);
-        if (ok && n < na) {
-          const float mu = z[j >> 2][j & 3];
-          float s, ls;
-          sigma_of(A.std_param[n], A.log_std, s, ls);
-          const float x = mu + s * noise_at(A, row, n), diff = x - mu;
-          lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
-          A.actions[row * na + n] = x;
-          A.s_act[row * na + n] = x;
-          A.s_mu[row * na + n] = mu;
-          A.s_sig[row * na + n] = s;
-        }
+        if (ok && n < A.na) lp += sample_action(A, row, n, z[j >> 2][j & 3]);
       }
       lp = rr_feat_sum(lp);
       if (ok && gq == 0) A.s_lp[row] = lp;
@@ -1458,21 +1465,9 @@ __global__ __launch_bounds__(256, 2) void k_act_split(ActArgs A) {
   const int net = blockIdx.x & 1;
   const int64_t row = (int64_t)(blockIdx.x >> 1) * 16 + r;
   const bool ok = row < A.rows;
-  const int na = A.na;
   const NetW& w = A.n[net];
   Tile x0[2], x1[T1], x2[T2], x3[T3];
-  {
-    const int dim = net ? A.cobs_dim : A.obs_dim;
-    const float* src = (net ? A.cobs : A.obs) + row * dim;
-    float* st = (net ? A.s_cobs : A.s_obs) + row * dim;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = 16 * (j >> 2) + 4 * gq + (j & 3);
-      const float v = (ok && k < dim) ? src[k] : 0.f;
-      x0[j >> 2][j & 3] = (kNorm && A.nrm[net].mean && ok && k < dim) ? obs_normalize(A.nrm[net], k, v) : v;
-      if (wv == 0 && ok && k < dim) st[k] = v;
-    }
-  }
+  act_rr_gather<kNorm>(A, net, row, ok, wv == 0, x0);
   as_layer<2, T1, kAct>(A.ws + w.wr[0], A.ws + w.bp[0], x0, x1, xs[0], wv, lane);
   as_layer<T1, T2, kAct>(A.ws + w.wr[1], A.ws + w.bp[1], x1, x2, xs[1], wv, lane);
   as_layer<T2, T3, kAct>(A.ws + w.wr[2], A.ws + w.bp[2], x2, x3, xs[0], wv, lane);
@@ -1494,22 +1489,11 @@ __global__ __launch_bounds__(256, 2) void k_act_split(ActArgs A) {
   }
   if (net == 0) {
     // lane (r, g) holds actions 4 g + u of row r
-    const float kLog2Pi = 0.91893853320467274178f;  // log(sqrt(2 pi))
     float lp = 0.f;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int n = 4 * gq + u;
-      if (ok && n < na) {
-        const float mu = z[u];
-        float s, ls;
-        sigma_of(A.std_param[n], A.log_std, s, ls);
-        const float x = mu + s * noise_at(A, row, n), diff = x - mu;
-        lp += -(diff * diff) / (2.f * (s * s)) - ls - kLog2Pi;
-        A.actions[row * na + n] = x;
-        A.s_act[row * na + n] = x;
-        A.s_mu[row * na + n] = mu;
-        A.s_sig[row * na + n] = s;
-      }
+      if (ok && n < A.na) lp += sample_action(A, row, n, z[u]);
     }
     lp = rr_feat_sum(lp);
     if (ok && gq == 0) A.s_lp[row] = lp;
@@ -1768,40 +1752,68 @@ int launch_check(const char* what) {
 // The register kernels per activation. ELU (every shipped cfg) keeps its two instantiations, with and
 // without the normalizer's code; the other activations have one each, the kNorm one, which tests the
 // normalizer's pointer at run time (half the instantiations to compile).
+// f(activation, kNorm), both std::integral_constants, for exactly that set.
+template <class F>
+void with_act_norm(int act, bool norm, F&& f) {
+  with_act(act, [&](auto a) {
+    if constexpr (decltype(a)::value == ZBP_ACT_ELU) {
+      if (!norm) return f(a, std::false_type{});
+    }
+    return f(a, std::true_type{});
+  });
+}
 template <int T1, int T2, int T3>
 void launch_rows_reg(int act, bool norm, int grid, hipStream_t s, const RowArgs& R) {
-  switch (act) {
-    case ZBP_ACT_RELU: k_rows_reg<T1, T2, T3, true, ZBP_ACT_RELU><<<grid, RR_WG, 0, s>>>(R); break;
-    case ZBP_ACT_TANH: k_rows_reg<T1, T2, T3, true, ZBP_ACT_TANH><<<grid, RR_WG, 0, s>>>(R); break;
-    case ZBP_ACT_SELU: k_rows_reg<T1, T2, T3, true, ZBP_ACT_SELU><<<grid, RR_WG, 0, s>>>(R); break;
-    case ZBP_ACT_LRELU: k_rows_reg<T1, T2, T3, true, ZBP_ACT_LRELU><<<grid, RR_WG, 0, s>>>(R); break;
-    default:
-      if (norm) k_rows_reg<T1, T2, T3, true, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(R);
-      else k_rows_reg<T1, T2, T3, false, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(R);
-  }
+  with_act_norm(act, norm, [&](auto a, auto n) {
+    k_rows_reg<T1, T2, T3, decltype(n)::value, decltype(a)::value><<<grid, RR_WG, 0, s>>>(R);
+  });
 }
 template <int T1, int T2, int T3>
 void launch_act_reg(int act, bool norm, int grid, hipStream_t s, const ActArgs& A) {
-  switch (act) {
-    case ZBP_ACT_RELU: k_act_reg<T1, T2, T3, true, ZBP_ACT_RELU><<<grid, RR_WG, 0, s>>>(A); break;
-    case ZBP_ACT_TANH: k_act_reg<T1, T2, T3, true, ZBP_ACT_TANH><<<grid, RR_WG, 0, s>>>(A); break;
-    case ZBP_ACT_SELU: k_act_reg<T1, T2, T3, true, ZBP_ACT_SELU><<<grid, RR_WG, 0, s>>>(A); break;
-    case ZBP_ACT_LRELU: k_act_reg<T1, T2, T3, true, ZBP_ACT_LRELU><<<grid, RR_WG, 0, s>>>(A); break;
-    default:
-      if (norm) k_act_reg<T1, T2, T3, true, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(A);
-      else k_act_reg<T1, T2, T3, false, ZBP_ACT_ELU><<<grid, RR_WG, 0, s>>>(A);
-  }
+  with_act_norm(act, norm, [&](auto a, auto n) {
+    k_act_reg<T1, T2, T3, decltype(n)::value, decltype(a)::value><<<grid, RR_WG, 0, s>>>(A);
+  });
 }
 void launch_act_split(int act, bool norm, int grid, hipStream_t s, const ActArgs& A) {
-  switch (act) {
-    case ZBP_ACT_RELU: k_act_split<8, 8, 8, true, ZBP_ACT_RELU><<<grid, 256, 0, s>>>(A); break;
-    case ZBP_ACT_TANH: k_act_split<8, 8, 8, true, ZBP_ACT_TANH><<<grid, 256, 0, s>>>(A); break;
-    case ZBP_ACT_SELU: k_act_split<8, 8, 8, true, ZBP_ACT_SELU><<<grid, 256, 0, s>>>(A); break;
-    case ZBP_ACT_LRELU: k_act_split<8, 8, 8, true, ZBP_ACT_LRELU><<<grid, 256, 0, s>>>(A); break;
-    default:
-      if (norm) k_act_split<8, 8, 8, true, ZBP_ACT_ELU><<<grid, 256, 0, s>>>(A);
-      else k_act_split<8, 8, 8, false, ZBP_ACT_ELU><<<grid, 256, 0, s>>>(A);
+  with_act_norm(act, norm, [&](auto a, auto n) {
+    k_act_split<8, 8, 8, decltype(n)::value, decltype(a)::value><<<grid, 256, 0, s>>>(A);
+  });
+}
+
+// The LDS row tile of k_rows / k_act (float offsets): X_l [32][p(l) + 4] of every layer (the wider of the
+// two nets), then (dz != nullptr: the minibatch pass) the output layer's dZ [32][32 + 4], the output
+// pre-activations [32][33], and (red != nullptr) the NSTAT per-tile sums. Refuses a tile over the CU's
+// 160 KB and raises the kernel's dynamic-LDS limit on its first call (a host-side attribute: set once per
+// kernel, outside any stream capture's ops). *bytes: the launch's dynamic LDS.
+template <class Args>
+int lds_row_tile(const Layout& lo, void (*kernel)(Args), const char* api, const char* name, int (&x)[MAXL], int* dz,
+                 int& out, int* red, size_t* bytes) {
+  int off = 0;
+  for (int l = 0; l < MAXL; ++l) {
+    const int p = lo.n[0].p[l] > lo.n[1].p[l] ? lo.n[0].p[l] : lo.n[1].p[l];
+    x[l] = off;
+    off += TR * (p + 4);
   }
+  if (dz) { *dz = off; off += TR * (32 + 4); }
+  out = off;
+  off += TR * 33;
+  if (red) { *red = off; off += NSTAT; }
+  *bytes = sizeof(float) * off;
+  char what[96];
+  if (*bytes > 160 * 1024) {
+    snprintf(what, sizeof(what), "%s: nets too wide for the LDS row tile", api);
+    return fail(-1, what);
+  }
+  static bool lds_set = false;  // (one per Args type, i.e. per kernel)
+  if (!lds_set) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {
+      snprintf(what, sizeof(what), "hipFuncSetAttribute %s", name);
+      return hip_fail(e, what);
+    }
+    lds_set = true;
+  }
+  return 0;
 }
 
 PackArgs pack_args(const Layout& lo, const zbp_net* a, const zbp_net* c, float* ws) {
@@ -1879,26 +1891,8 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   R.ws = ws;
   R.stats = lo.stats;
   R.B = B;
-  int off = 0;
-  for (int l = 0; l < MAXL; ++l) {
-    const int p = lo.n[0].p[l] > lo.n[1].p[l] ? lo.n[0].p[l] : lo.n[1].p[l];
-    R.lds_x[l] = off;
-    off += TR * (p + 4);
-  }
-  R.lds_dz = off;  // the output layer's dZ ([32][p(L) + 4], p(L) = 32)
-  off += TR * (32 + 4);
-  R.lds_out = off;
-  off += TR * 33;
-  R.lds_red = off;
-  off += NSTAT;
-  const size_t lds = sizeof(float) * off;
-  if (lds > 160 * 1024) return fail(-1, "zbp_minibatch: nets too wide for the LDS row tile");
-  static bool lds_set = false;  // (a host-side attribute: set once, outside any stream capture's ops)
-  if (!lds_set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute k_rows");
-    lds_set = true;
-  }
+  size_t lds;
+  if (int rc = lds_row_tile(lo, k_rows, "zbp_minibatch", "k_rows", R.lds_x, &R.lds_dz, R.lds_out, &R.lds_red, &lds)) return rc;
   // the register-resident row kernel for the shipped shapes (ZBP_ROWS=lds: the LDS one, for A/Bs)
   const int shape = reg_shape(lo, B);
   const bool norm = batch->actor_norm.mean || batch->critic_norm.mean;
@@ -1913,27 +1907,17 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   WgradArgs W{};
   W.n[0] = lo.n[0];
   W.n[1] = lo.n[1];
-  for (int i = 0; i <= 2 * MAXL; ++i) W.tile0[i] = lo.tile0[i];
-  for (int i = 0; i <= 2 * MAXL; ++i) W.grp0[i] = lo.grp0[i];
-  for (int i = 0; i <= 2 * MAXL; ++i) W.blk0[i] = lo.blk0[i];
-  for (int i = 0; i < 2 * MAXL; ++i) W.sp_nl[i] = lo.sp_nl[i];
-  for (int i = 0; i < 2 * MAXL; ++i) W.ord[i] = lo.ord[i];
-  W.wtiles = lo.wtiles;
-  W.ngroups = lo.ngroups;
-  W.splits = lo.splits;
+  W.tm = lo.tm;
   W.batch = B;
   W.ws = ws;
   W.part = lo.part;
-  k_wgrad<<<lo.blk0[2 * MAXL], 256, 0, s>>>(W);
+  k_wgrad<<<lo.tm.blk0[2 * MAXL], 256, 0, s>>>(W);
   if (int rc = launch_check("k_wgrad")) return rc;
 
   ReduceArgs D{};
   D.n[0] = lo.n[0];
   D.n[1] = lo.n[1];
-  for (int i = 0; i <= 2 * MAXL; ++i) D.tile0[i] = lo.tile0[i];
-  D.wtiles = lo.wtiles;
-  D.splits = lo.splits;
-  for (int i = 0; i < 2 * MAXL; ++i) D.sp_nl[i] = lo.sp_nl[i];
+  D.tm = lo.tm;
   D.row_tiles = shape ? B / RR_TR : B / TR;
   D.batch = B;
   D.num_actions = batch->num_actions;
@@ -1953,7 +1937,7 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   D.part = lo.part;
   D.rstats = lo.stats;
   D.norm2 = ws + lo.scratch;
-  k_reduce<<<lo.wtiles + 1, RED_THREADS, 0, s>>>(D);
+  k_reduce<<<lo.tm.wtiles + 1, RED_THREADS, 0, s>>>(D);
   return launch_check("k_reduce");
 }
 
@@ -1979,7 +1963,7 @@ int zbp_optimizer_step(const zbp_params* params, float* lr, const float* stats, 
   O.total = 0;
   for (int t = 0; t < params->n_params; ++t) O.total += params->numel[t];
   if (norm_from_minibatch) {
-    O.nparts = lo.wtiles + 1;  // k_reduce's per-tile sums of the gradients it wrote
+    O.nparts = lo.tm.wtiles + 1;  // k_reduce's per-tile sums of the gradients it wrote
   } else {
     O.nparts = 64;
     k_norm<<<64, 256, 0, s>>>(O);
@@ -2036,22 +2020,8 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
   A.nrm[0] = io->actor_norm;
   A.nrm[1] = io->critic_norm;
   A.log_std = io->log_std;
-  int off = 0;
-  for (int l = 0; l < MAXL; ++l) {
-    const int p = lo.n[0].p[l] > lo.n[1].p[l] ? lo.n[0].p[l] : lo.n[1].p[l];
-    A.lds_x[l] = off;
-    off += TR * (p + 4);
-  }
-  A.lds_out = off;
-  off += TR * 33;
-  const size_t lds = sizeof(float) * off;
-  if (lds > 160 * 1024) return fail(-1, "zbp_act: nets too wide for the LDS row tile");
-  static bool lds_set = false;
-  if (!lds_set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_act, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute k_act");
-    lds_set = true;
-  }
+  size_t lds;
+  if (int rc = lds_row_tile(lo, k_act, "zbp_act", "k_act", A.lds_x, nullptr, A.lds_out, nullptr, &lds)) return rc;
   // (the register-resident forward, actor and critic in separate workgroups, from ZBP_ACT_REG_MIN rows
   // (4096): 23.5 us against the LDS kernel's 34.9 at 4096 rows (before the split 42 us: too few
   // workgroups), 146 against 242 at 32 768 (profiles/r5y); ZBP_ACT=lds / reg for A/Bs)
