@@ -67,6 +67,46 @@ typedef struct {
   int32_t dim;     /* the net's observation dim (<= 32) */
 } zbp_obs_norm;
 
+/* rsl_rl's symmetry option (PPO `symmetry_cfg`; zbot_lab_amd/rl/symmetry.py SignedPermutation) for ONE
+ * mirror map, a signed permutation per tensor:
+ *   obs_m[k] = obs_sign[k] obs[obs_perm[k]],  cobs_m[k] = critic_sign[k] cobs[critic_perm[k]],
+ *   act_m[a] = act_sign[a] act[act_perm[a]].
+ * On (augment or mirror_loss or loss_acc != NULL) a minibatch of B = zbp_batch.batch samples is 2 B kernel
+ * rows: sample j and its mirror both read row idx[idx_offset + j] of the rollout; the mirror applies the map
+ * in the gather, BEFORE the normalizer (column k is normalized with the statistics of column k: rsl_rl's
+ * normalizer sits inside the policy), to the observations, the critic observations and the actions, and
+ * reuses the sample's log_prob, values, advantages and returns. Terms (rsl_rl PPO.update):
+ *   surrogate, value loss   augment: means over the 2 B rows; otherwise over the B originals (the mirrored
+ *                           rows get zero weight; they still run the critic's forward and a backward of
+ *                           zeros -- the price of one launch shape for the three modes)
+ *   KL, entropy             means over the B originals, always
+ *   symmetry loss           mean over the B mirrored rows and the actions of (mu_m[a] - act_sign[a]
+ *                           mu_o[act_perm[a]])^2, mu_o the original's mean, taken as a constant: with
+ *                           mirror_loss, mirror_coef times its gradient goes into the mirrored row only,
+ *                           dL / dmu_m[a] += mirror_coef 2 (mu_m[a] - target) / (B num_actions);
+ *                           loss_acc[0] += the loss, with or without mirror_loss.
+ * The row kernels hold an original next to its mirror in one tile (8 + 8 rows of k_rows_reg's 16-row tile,
+ * 16 + 16 of k_rows' 32-row tile), so the pairing costs no launch; row order only changes fp32 summation
+ * order. All zero: off, exactly the behaviour without the member.
+ * Workspace rule: with symmetry on, the `batch` argument of zbp_workspace_floats, zbp_pack, zbp_act and
+ * zbp_optimizer_step is the kernel row count 2 B; ws_batch states it here, and zbp_minibatch refuses
+ * ws_batch != 2 * zbp_batch.batch before any launch (off: ws_batch is ignored).
+ * The tables are device arrays the caller keeps valid; a perm entry outside [0, dim) is clamped into it
+ * (never an out-of-bounds read; the result is then meaningless). */
+typedef struct {
+  const int32_t* obs_perm;     /* [obs_dim] */
+  const float* obs_sign;       /* [obs_dim] +-1 */
+  const int32_t* critic_perm;  /* [critic_obs_dim] */
+  const float* critic_sign;    /* [critic_obs_dim] */
+  const int32_t* act_perm;     /* [num_actions] */
+  const float* act_sign;       /* [num_actions] */
+  int32_t augment;             /* use_data_augmentation */
+  int32_t mirror_loss;         /* use_mirror_loss */
+  float mirror_coef;           /* mirror_loss_coeff */
+  int32_t ws_batch;            /* the workspace's batch (kernel rows): 2 * zbp_batch.batch */
+  float* loss_acc;             /* [1] += the minibatch's symmetry loss, or NULL */
+} zbp_symmetry;
+
 /* The rollout (RolloutStorage, flattened [T * N] rows) and this minibatch's rows:
  * rows idx[idx_offset .. idx_offset + batch) of the permutation (int64, rsl_rl's randperm). */
 typedef struct {
@@ -85,6 +125,7 @@ typedef struct {
   int32_t obs_dim, critic_obs_dim, num_actions;
   zbp_obs_norm actor_norm;   /* applied to the gathered obs rows (mean == NULL: none) */
   zbp_obs_norm critic_norm;  /* applied to the gathered critic_obs rows */
+  zbp_symmetry symmetry;     /* all zero: off */
 } zbp_batch;
 
 /* PPO loss constants (RslRlPpoAlgorithmCfg) */
@@ -99,7 +140,9 @@ typedef struct {
 } zbp_loss_cfg;
 
 /* Workspace floats for nets of these shapes and minibatch size (the caller allocates one float
- * buffer of that size, 256-byte aligned, and passes it to every call). */
+ * buffer of that size, 256-byte aligned, and passes it to every call). `batch` here and in zbp_pack,
+ * zbp_act and zbp_optimizer_step is the minibatch's kernel rows: zbp_batch.batch, or twice that with
+ * zbp_batch.symmetry on (zbp_symmetry, the workspace rule). */
 int64_t zbp_workspace_floats(const zbp_net* actor, const zbp_net* critic, int32_t batch);
 
 /* Copy the current parameters into the workspace's padded / transposed images. Call once before

@@ -56,6 +56,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--critic_obs", action="store_true", default=False,
                     help="asymmetric actor-critic: the env also returns the privileged \"critic\" observation group "
                          "(env cfg critic_observations) and the runner feeds the critic from it")
+    ap.add_argument("--symmetry", default=None, metavar="FILE.json",
+                    help="rsl_rl symmetry_cfg: a JSON file with the mirror map's tables obs_perm, obs_sign, act_perm, "
+                         "act_sign and (optional) critic_obs_perm, critic_obs_sign (rl/symmetry.SignedPermutation); "
+                         "no map of the robot ships with the project (INTEGRATION.md)")
+    ap.add_argument("--symmetry_mode", choices=("aug", "mirror", "both"), default="both",
+                    help="with --symmetry: data augmentation, the mirror loss, or both")
+    ap.add_argument("--mirror_loss_coeff", type=float, default=0.5, help="with --symmetry: the mirror loss's weight")
     ap.add_argument("--env", action="append", default=[], metavar="PATH=VALUE",
                     help="env cfg override by dotted path, e.g. solver.iterations=8 (simulator ablations)")
     return ap
@@ -78,6 +85,15 @@ def update_rsl_rl_cfg(agent_cfg, args):
         agent_cfg.run_name = args.run_name
     if args.experiment_name is not None:
         agent_cfg.experiment_name = args.experiment_name
+    if getattr(args, "symmetry", None):
+        from zbot_lab_amd.rl.cfg import RslRlSymmetryCfg
+        from zbot_lab_amd.rl.symmetry import SignedPermutation
+        with open(args.symmetry) as f:
+            func = SignedPermutation.from_dict(json.load(f))
+        agent_cfg.algorithm.symmetry_cfg = RslRlSymmetryCfg(
+            use_data_augmentation=args.symmetry_mode in ("aug", "both"),
+            use_mirror_loss=args.symmetry_mode in ("mirror", "both"), mirror_loss_coeff=args.mirror_loss_coeff,
+            data_augmentation_func=func)
     return agent_cfg
 
 

@@ -17,6 +17,9 @@
 //                128 x 128 output blocks, split-K over row ranges sized to one round of the device's
 //                resident workgroups; partial tiles to the workspace
 //   k_reduce     partial tiles -> every parameter's .grad, the std gradient, the minibatch stats
+//   (rsl_rl's symmetry option, zbp_symmetry: the kSym instantiations of k_rows_reg, k_rows_sym and
+//   k_reduce_sym run 2 B rows, every original next to its mirror image in one row tile; off, the kernels
+//   above are the code they were)
 //
 // and, on one GPU, k_adam (adaptive learning rate, global-norm clipping from k_reduce's per-tile sums
 // of squares, or k_norm's, Adam) + the re-pack (k_pack, which also writes the new rate and step); the rollout's policy step (k_act_reg / k_act), its bookkeeping (k_env_post) and
@@ -108,6 +111,7 @@ struct Layout {
   TileMap tm;
   int64_t scratch;  // [max(64, wtiles + 1)] gradient sums of squares: k_norm's per block, or k_reduce's per weight tile
   int64_t rng;      // [1] uint32: the draw counter of the in-kernel action noise, advanced by every k_pack
+  int64_t sym;      // [B / 16] per-row-tile sums of the symmetry loss's squared errors (zbp_symmetry; last, so every other offset is as without it)
   int64_t total;
 };
 
@@ -197,6 +201,7 @@ Layout make_layout(const zbp_net* a, const zbp_net* c, int B) {
   lo.part = take((int64_t)s * t * PART);
   lo.scratch = take(t + 1 > 64 ? t + 1 : 64);
   lo.rng = take(1);
+  lo.sym = take(B / 16);
   lo.total = off;
   return lo;
 }
@@ -432,7 +437,27 @@ struct RowArgs {
   int64_t stats;
   int B;
   int lds_x[MAXL], lds_dz, lds_out, lds_red;  // LDS float offsets
+  // zbp_symmetry on (the kSym kernels only): 1 / rows the losses average, the mirror term's factor
+  // mirror_coef 2 / (B num_actions) (0 without mirror_loss), the per-tile squared-error sums
+  float sym_inv_loss, sym_grad;
+  int64_t sym_part;
 };
+
+// ---- zbp_symmetry in the row kernels. Kernel row kr of a tile of TS rows: the tile's first TS / 2 rows are
+// originals, the others their mirrors; both are sample (kr / TS) (TS / 2) + (kr mod TS / 2) of the minibatch
+template <int TS>
+__device__ __forceinline__ int sym_sample(int kr) { return (kr / TS) * (TS / 2) + (kr & (TS / 2 - 1)); }
+template <int TS>
+__device__ __forceinline__ bool sym_mirrored(int kr) { return (kr & (TS - 1)) >= TS / 2; }
+// column k of a row x under the map (perm, sign) when mirrored, x[k] itself otherwise (a perm entry
+// outside [0, dim) is clamped: never an out-of-bounds read)
+__device__ __forceinline__ float sym_at(const float* x, int k, int dim, bool mir, const int32_t* perm, const float* sign) {
+  if (!mir) return x[k];
+  const int p = min(max(perm[k], 0), dim - 1);
+  return sign[k] * x[p];
+}
+// a row's weight in the surrogate and the value loss: mirrored rows count only under augmentation
+__device__ __forceinline__ float sym_loss_weight(const zbp_symmetry& sy, bool mir) { return (mir && !sy.augment) ? 0.f : 1.f; }
 
 // forward through one net for the row tile; the output layer's pre-activations land in `out`
 // ([32][33]). kStore: every hidden layer's input X_l also goes to the HBM row buffers (feature-major,
@@ -513,13 +538,15 @@ __device__ __forceinline__ float obs_normalize(const zbp_obs_norm& nr, int k, fl
 
 // gather the tile's input rows (obs or critic obs) into X_0 (LDS + HBM), zero-padded; normalized
 // when the net has a normalizer (nr.mean != NULL)
-__device__ void gather_input(const RowArgs& A, const NetW& w, const float* src, int dim, const zbp_obs_norm& nr,
-                             float* lds, int row0) {
+// (kSym: the tile's rows 16 .. 31 are the mirrors of rows 0 .. 15 under (perm, sign), mapped before the normalizer)
+template <bool kSym>
+__device__ __forceinline__ void gather_input(const RowArgs& A, const NetW& w, const float* src, int dim, const zbp_obs_norm& nr,
+                                             float* lds, int row0, const int32_t* perm = nullptr, const float* sign = nullptr) {
   const int P0 = w.p[0];
   for (int e = threadIdx.x; e < TR * P0; e += blockDim.x) {
     const int k = e / TR, i = e % TR;
-    const int64_t row = A.bt.idx[A.bt.idx_offset + row0 + i];
-    float v = k < dim ? src[row * dim + k] : 0.f;
+    const int64_t row = A.bt.idx[A.bt.idx_offset + (kSym ? sym_sample<TR>(row0 + i) : row0 + i)];
+    float v = k < dim ? (kSym ? sym_at(src + row * dim, k, dim, sym_mirrored<TR>(i), perm, sign) : src[row * dim + k]) : 0.f;
     if (nr.mean && k < dim) v = obs_normalize(nr, k, v);
     lds[A.lds_x[0] + i * (P0 + 4) + k] = v;
     A.ws[w.x[0] + rbo(P0, k, row0 + i)] = v;
@@ -532,49 +559,61 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-__global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
-  extern __shared__ float lds[];
+template <bool kSym>
+__device__ __forceinline__ void rows_body(const RowArgs& A, float* lds) {
   const int row0 = blockIdx.x * TR;
   const int tid = threadIdx.x;
   const zbp_batch& bt = A.bt;
+  const zbp_symmetry& sy = bt.symmetry;
   const int NA = bt.num_actions;
-  const float invB = 1.f / (float)bt.batch;
+  const float invB = kSym ? A.sym_inv_loss : 1.f / (float)bt.batch;
   float* red = lds + A.lds_red;  // [NSTAT] per-tile sums
   if (tid < NSTAT) red[tid] = 0.f;
 
   // ---- actor: forward, Gaussian log-prob, clipped surrogate, KL; dL/dmu into dZ of the output
   const NetW& wa = A.n[0];
-  gather_input(A, wa, bt.obs, bt.obs_dim, bt.actor_norm, lds, row0);
+  gather_input<kSym>(A, wa, bt.obs, bt.obs_dim, bt.actor_norm, lds, row0, sy.obs_perm, sy.obs_sign);
   net_forward(A, wa, lds, row0);
   {
     float* dz = lds + A.lds_dz;
     const int Pout = wa.p[wa.L];
-    float surr = 0.f, kl = 0.f, sg[NSTAT - 3];
+    float surr = 0.f, kl = 0.f, sg[NSTAT - 3], se = 0.f;
 #pragma unroll
     for (int a = 0; a < NSTAT - 3; ++a) sg[a] = 0.f;
     if (tid < TR) {
       const int i = tid;
-      const int64_t row = bt.idx[bt.idx_offset + row0 + i];
+      const bool mir = kSym && sym_mirrored<TR>(i);
+      const float wl = kSym ? sym_loss_weight(sy, mir) : 1.f;
+      const int64_t row = bt.idx[bt.idx_offset + (kSym ? sym_sample<TR>(row0 + i) : row0 + i)];
+      const float* arow = bt.actions + row * NA;
       float lp = 0.f;
       for (int a = 0; a < NA; ++a) {
         const float mu = lds[A.lds_out + i * 33 + a];
         float s, ls;
         sigma_of(A.std_param[a], A.lc.log_std, s, ls);
-        lp += logp_term(bt.actions[row * NA + a] - mu, s, ls);
-        kl += kl_term(mu, s, bt.mu[row * NA + a], bt.sigma[row * NA + a]);
+        lp += logp_term((kSym ? sym_at(arow, a, NA, mir, sy.act_perm, sy.act_sign) : arow[a]) - mu, s, ls);
+        if (!mir) kl += kl_term(mu, s, bt.mu[row * NA + a], bt.sigma[row * NA + a]);  // (the KL: originals only)
       }
       float g;
-      surrogate(expf(lp - bt.log_prob[row]), bt.advantages[row], A.lc.clip_param, invB, surr, g);
+      surrogate(expf(lp - bt.log_prob[row]), bt.advantages[row], A.lc.clip_param, kSym ? wl * invB : invB, surr, g);
+      if (kSym) surr *= wl;
       for (int a = 0; a < Pout; ++a) {
         float d = 0.f;
         if (a < NA) {
           const float mu = lds[A.lds_out + i * 33 + a];
           float s, ls, ds;
           sigma_of(A.std_param[a], A.lc.log_std, s, ls);
-          gauss_grad(g, bt.actions[row * NA + a] - mu, s, d, ds);
+          gauss_grad(g, (kSym ? sym_at(arow, a, NA, mir, sy.act_perm, sy.act_sign) : arow[a]) - mu, s, d, ds);
 #pragma unroll
           for (int b = 0; b < NSTAT - 3; ++b)
             if (b == a) sg[b] = ds;
+          if (mir) {
+            // the mirror term: this row's mean against the mapped mean of its original (row i - 16 of the
+            // output tile), a constant; its gradient stays in this row
+            const float e = mu - sym_at(lds + A.lds_out + (i - TR / 2) * 33, a, NA, true, sy.act_perm, sy.act_sign);
+            se += e * e;
+            d += A.sym_grad * e;
+          }
         }
         dz[i * (Pout + 4) + a] = d;
         A.ws[wa.dz[wa.L - 1] + rbo(Pout, a, row0 + i)] = d;
@@ -583,6 +622,10 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
     if (tid < 64) {
       surr = wave_sum(surr);
       kl = wave_sum(kl);
+      if (kSym) {
+        se = wave_sum(se);
+        if (tid == 0) A.ws[A.sym_part + blockIdx.x] = se;
+      }
 #pragma unroll
       for (int a = 0; a < NSTAT - 3; ++a) sg[a] = wave_sum(sg[a]);
       if (tid == 0) {
@@ -598,7 +641,7 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
 
   // ---- critic: forward, clipped value loss, backward
   const NetW& wc = A.n[1];
-  gather_input(A, wc, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, lds, row0);
+  gather_input<kSym>(A, wc, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, lds, row0, sy.critic_perm, sy.critic_sign);
   net_forward(A, wc, lds, row0);
   {
     float* dz = lds + A.lds_dz;
@@ -606,9 +649,11 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
     float vl = 0.f;
     if (tid < TR) {
       const int i = tid;
-      const int64_t row = bt.idx[bt.idx_offset + row0 + i];
+      const float wl = kSym ? sym_loss_weight(sy, sym_mirrored<TR>(i)) : 1.f;
+      const int64_t row = bt.idx[bt.idx_offset + (kSym ? sym_sample<TR>(row0 + i) : row0 + i)];
       float dv;
-      value_loss(lds[A.lds_out + i * 33], bt.values[row], bt.returns[row], A.lc, invB, vl, dv);
+      value_loss(lds[A.lds_out + i * 33], bt.values[row], bt.returns[row], A.lc, kSym ? wl * invB : invB, vl, dv);
+      if (kSym) vl *= wl;
       for (int a = 0; a < Pout; ++a) {
         dz[i * (Pout + 4) + a] = a == 0 ? dv : 0.f;
         A.ws[wc.dz[wc.L - 1] + rbo(Pout, a, row0 + i)] = a == 0 ? dv : 0.f;
@@ -622,6 +667,15 @@ __global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
   }
   net_backward(A, wc, lds, row0);
   if (tid < NSTAT) A.ws[A.stats + (int64_t)blockIdx.x * NSTAT + tid] = red[tid];
+}
+__global__ __launch_bounds__(ROW_THREADS) void k_rows(RowArgs A) {
+  extern __shared__ float lds[];
+  rows_body<false>(A, lds);
+}
+// (zbp_symmetry on: 16 originals + their 16 mirrors per tile)
+__global__ __launch_bounds__(ROW_THREADS) void k_rows_sym(RowArgs A) {
+  extern __shared__ float lds[];
+  rows_body<true>(A, lds);
 }
 
 // ------------------------------------------------------------------------------- k_rows_reg
@@ -778,24 +832,27 @@ __device__ __forceinline__ void rr_backward(const NetW& w, int l, float* __restr
 // for nets that have none, so those keep their code and register budget)
 // x[o][u] = feature 16 o + 4 g + u of the input row sr (ok: the row exists), normalized; st != nullptr
 // (the rollout's storage slot) gets the row as read
-template <bool kNorm>
-__device__ __forceinline__ void rr_input(const float* sr, int dim, const zbp_obs_norm& nr, bool ok, Tile (&x)[2], float* st) {
+// (kSym: a mirrored row reads through the signed permutation (perm, sign), before the normalizer)
+template <bool kNorm, bool kSym = false>
+__device__ __forceinline__ void rr_input(const float* sr, int dim, const zbp_obs_norm& nr, bool ok, Tile (&x)[2], float* st,
+                                         bool mir = false, const int32_t* perm = nullptr, const float* sign = nullptr) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int k = 16 * (j >> 2) + 4 * rr_g() + (j & 3);
     const bool in = ok && k < dim;
-    const float v = in ? sr[k] : 0.f;
+    const float v = in ? (kSym ? sym_at(sr, k, dim, mir, perm, sign) : sr[k]) : 0.f;
     x[j >> 2][j & 3] = (kNorm && nr.mean && in) ? obs_normalize(nr, k, v) : v;
     if (st && in) st[k] = v;
   }
 }
 // (the minibatch: the row through the permutation; X_0, normalized, also to its row buffer)
-template <bool kNorm>
+template <bool kNorm, bool kSym = false>
 __device__ __forceinline__ void rr_gather(const NetW& w, float* __restrict__ ws, int row0, const float* src, int dim,
-                                          const zbp_obs_norm& nr, int64_t row, Tile (&x)[2]) {
+                                          const zbp_obs_norm& nr, int64_t row, Tile (&x)[2], bool mir = false,
+                                          const int32_t* perm = nullptr, const float* sign = nullptr) {
   const int lo = rr_lane_off(32);
   float* xb = rr_base(ws + w.x[0], 32, row0);
-  rr_input<kNorm>(src + row * dim, dim, nr, true, x, nullptr);
+  rr_input<kNorm, kSym>(src + row * dim, dim, nr, true, x, nullptr, mir, perm, sign);
 #pragma unroll
   for (int o = 0; o < 2; ++o)
 #pragma unroll
@@ -846,7 +903,10 @@ __device__ __forceinline__ void rr_backward_chain(const NetW& w, float* __restri
 }
 
 constexpr int RR_TR = 16;  // rows per wave
-template <int T1, int T2, int T3, bool kNorm, int kAct>
+// kSym (zbp_symmetry on): the tile's rows 0 .. 7 are originals, rows 8 .. 15 their mirrors; a mirrored row's
+// lanes fetch the original's means from lanes (r - 8, any g) with ds_bpermute (the mean of action p sits in
+// lane (r, p >> 2), register p & 3 of output tile 0)
+template <int T1, int T2, int T3, bool kNorm, int kAct, bool kSym = false>
 __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   constexpr int CB = rr_cb<T1>();
   __shared__ float4 wl[2 * CB * 64];
@@ -857,9 +917,12 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   const int tile = (blockIdx.x >> 1) * (RR_WG / 64) + (threadIdx.x >> 6);  // (B a multiple of 64: reg_shape)
   const int row0 = tile * RR_TR;
   const zbp_batch& bt = A.bt;
+  const zbp_symmetry& sy = bt.symmetry;
   const int NA = bt.num_actions;
-  const float invB = 1.f / (float)bt.batch;
-  const int64_t row = bt.idx[bt.idx_offset + row0 + r];
+  const float invB = kSym ? A.sym_inv_loss : 1.f / (float)bt.batch;
+  const bool mir = kSym && sym_mirrored<RR_TR>(r);
+  const float wgt = kSym ? sym_loss_weight(sy, mir) : 1.f;
+  const int64_t row = bt.idx[bt.idx_offset + (kSym ? sym_sample<RR_TR>(row0 + r) : row0 + r)];
   float* ws = A.ws;
   float* st = ws + A.stats + (int64_t)tile * NSTAT;
   // the losses' inputs of this lane's row and actions (4 g + u, u < 4: num_actions <= 13 < 16), loaded
@@ -874,7 +937,7 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int n = 4 * gq + u;
-    act_in[u] = n < NA ? bt.actions[row * NA + n] : 0.f;
+    act_in[u] = n < NA ? (kSym ? sym_at(bt.actions + row * NA, n, NA, mir, sy.act_perm, sy.act_sign) : bt.actions[row * NA + n]) : 0.f;
     mu_in[u] = n < NA ? bt.mu[row * NA + n] : 0.f;
     sig_in[u] = n < NA ? bt.sigma[row * NA + n] : 1.f;
   }
@@ -883,7 +946,7 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   rr_fetch<2 * T1, CB>(ws + wa.wr[0], 0, wst);
   {
     Tile x0[2];
-    rr_gather<kNorm>(wa, ws, row0, bt.obs, bt.obs_dim, bt.actor_norm, row, x0);
+    rr_gather<kNorm, kSym>(wa, ws, row0, bt.obs, bt.obs_dim, bt.actor_norm, row, x0, mir, sy.obs_perm, sy.obs_sign);
     rr_forward_chain<T1, T2, T3, true, CB, kAct>(wa, ws, wl, row0, x0, z, wst, ws + wa.wtr[3]);
   }
   {
@@ -900,18 +963,44 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
         sigma_of(A.std_param[n], A.lc.log_std, sig[j], ls);
         diff[j] = act_in[j & 3] - mu;  // (n < NA only in tile 0: j < 4)
         lp += logp_term(diff[j], sig[j], ls);
-        kl += kl_term(mu, sig[j], mu_in[j & 3], sig_in[j & 3]);
+        if (!mir) kl += kl_term(mu, sig[j], mu_in[j & 3], sig_in[j & 3]);  // (the KL: originals only)
       }
     }
     lp = rr_feat_sum(lp);
     kl = rr_feat_sum(kl);
     float surr, g;
-    surrogate(expf(lp - lp_in), adv_in, A.lc.clip_param, invB, surr, g);
+    surrogate(expf(lp - lp_in), adv_in, A.lc.clip_param, kSym ? wgt * invB : invB, surr, g);
+    if (kSym) surr *= wgt;
+    // the mirror term (kSym): err[u] = this mirrored row's mean of action 4 g + u minus the mapped mean of its
+    // original, a constant (every lane takes part in the exchange; only mirrored rows use the result)
+    float err[4] = {0.f, 0.f, 0.f, 0.f};
+    if (kSym) {
+      float se = 0.f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int n = 4 * gq + u;
+        const int p = n < NA ? min(max(sy.act_perm[n], 0), NA - 1) : 0;
+        const int srcl = (r & 7) + 16 * (p >> 2);
+        float t = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float c = __shfl(z[0][q], srcl);
+          if ((p & 3) == q) t = c;
+        }
+        if (mir && n < NA) {
+          err[u] = z[0][u] - sy.act_sign[n] * t;
+          se += err[u] * err[u];
+        }
+      }
+      se = wave_sum(se);
+      if (lane == 0) ws[A.sym_part + tile] = se;
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int n = 16 * (j >> 2) + 4 * gq + (j & 3);
       float d = 0.f, sg = 0.f;
       if (n < NA) gauss_grad(g, diff[j], sig[j], d, sg);
+      if (kSym && j < 4) d += A.sym_grad * err[j];
       dz[j >> 2][j & 3] = d;
       sg = rr_row_sum(sg);  // the std gradient summed over the tile's rows
       if (r == 0 && n < NA) st[3 + n] = sg;
@@ -931,12 +1020,14 @@ __global__ __launch_bounds__(RR_WG, rr_occ<T1>()) void k_rows_reg(RowArgs A) {
   rr_fetch<2 * T1, CB>(ws + wc.wr[0], 0, wst);
   {
     Tile x0[2];
-    rr_gather<kNorm>(wc, ws, row0, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, row, x0);
+    rr_gather<kNorm, kSym>(wc, ws, row0, bt.critic_obs, bt.critic_obs_dim, bt.critic_norm, row, x0, mir, sy.critic_perm,
+                           sy.critic_sign);
     rr_forward_chain<T1, T2, T3, true, CB, kAct>(wc, ws, wl, row0, x0, z, wst, ws + wc.wtr[3]);
   }
   {
     float vl, dv;
-    value_loss(__shfl(z[0][0], r), tv_in, ret_in, A.lc, invB, vl, dv);
+    value_loss(__shfl(z[0][0], r), tv_in, ret_in, A.lc, kSym ? wgt * invB : invB, vl, dv);
+    if (kSym) vl *= wgt;
 #pragma unroll
     for (int j = 0; j < 8; ++j) dz[j >> 2][j & 3] = (gq == 0 && j == 0) ? dv : 0.f;
     rr_store_dz(wc, ws, row0, dz);
@@ -1094,13 +1185,19 @@ struct ReduceArgs {
   const float* ws;
   int64_t part, rstats;
   float* norm2;  // [wtiles + 1]: each tile's sum of squared gradients (the last: the std's), for zbp_optimizer_step
+  // zbp_symmetry on (k_reduce_sym only): the samples B the KL averages over, the rows the losses average
+  // over (2 B under augmentation), the per-row-tile squared-error sums and the caller's accumulator
+  int sym_samples, sym_loss_rows;
+  int64_t sym_part;
+  float* sym_acc;
 };
 // one workgroup per weight tile: the split partials summed in order into .grad (weights of the tile,
 // and the bias for k0 = 0) and the tile's sum of their squares (fixed order); the last workgroup: the
 // scalars. 1024 threads: a thread sums one partial element over the splits with 16 loads in flight
 // (with 256 threads and 8 in flight the launch waited on ~30 dependent rounds of partial loads)
 constexpr int RED_THREADS = 1024;
-__global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
+template <bool kSym>
+__device__ __forceinline__ void reduce_body(const ReduceArgs& A) {
   if (blockIdx.x == (unsigned)A.tm.wtiles) {
     // per-row-tile sums -> stats, the std gradient (+ the entropy bonus term): thread t < 256 sums row
     // tiles t, t + 256, ... (one row = 16 floats = four float4, two rows in flight), then a fixed-order
@@ -1131,22 +1228,31 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
     if (t < 256)
 #pragma unroll
       for (int q = 0; q < NSTAT; ++q) red[t][q] = sv[q];
+    if (kSym && t < 256) {
+      // the symmetry loss's per-tile sums, the same way (the spare column of `red`)
+      float se = 0.f;
+      for (int k = t; k < A.row_tiles; k += 256) se += A.ws[A.sym_part + k];
+      red[t][NSTAT] = se;
+    }
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
-      if (t < st)
+      if (t < st) {
 #pragma unroll
         for (int q = 0; q < NSTAT; ++q) red[t][q] += red[t + st][q];
+        if (kSym) red[t][NSTAT] += red[t + st][NSTAT];
+      }
       __syncthreads();
     }
     if (threadIdx.x == 0) {
       float tot[NSTAT];
       for (int q = 0; q < NSTAT; ++q) tot[q] = red[0][q];
-      const float invB = 1.f / (float)A.batch;
+      const float invB = 1.f / (float)(kSym ? A.sym_loss_rows : A.batch);
       float ent = 0.f;
       // (log std: the parameter is log sigma)
       for (int a = 0; a < A.num_actions; ++a)
         ent += 0.5f + kLog2Pi + (A.log_std ? A.std_param[a] : logf(A.std_param[a]));
-      A.stats[0] = tot[2] * invB;  // kl mean
+      if (kSym && A.sym_acc) A.sym_acc[0] += red[0][NSTAT] / ((float)A.sym_samples * (float)A.num_actions);
+      A.stats[0] = tot[2] * (kSym ? 1.f / (float)A.sym_samples : invB);  // kl mean (symmetry: over the originals)
       A.stats[1] = tot[1] * invB;  // value loss
       A.stats[2] = tot[0] * invB;  // surrogate loss
       A.stats[3] = ent;            // entropy (every row's)
@@ -1207,6 +1313,8 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) {
     A.norm2[tile] = v;
   }
 }
+__global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceArgs A) { reduce_body<false>(A); }
+__global__ __launch_bounds__(RED_THREADS) void k_reduce_sym(ReduceArgs A) { reduce_body<true>(A); }
 
 // ------------------------------------------------------------------------------- k_optim
 struct OptimArgs {
@@ -1762,8 +1870,13 @@ void with_act_norm(int act, bool norm, F&& f) {
     return f(a, std::true_type{});
   });
 }
+// (sym: the zbp_symmetry instantiations, one per activation: the kNorm ones, as the non-ELU activations above)
 template <int T1, int T2, int T3>
-void launch_rows_reg(int act, bool norm, int grid, hipStream_t s, const RowArgs& R) {
+void launch_rows_reg(int act, bool norm, bool sym, int grid, hipStream_t s, const RowArgs& R) {
+  if (sym) {
+    with_act(act, [&](auto a) { k_rows_reg<T1, T2, T3, true, decltype(a)::value, true><<<grid, RR_WG, 0, s>>>(R); });
+    return;
+  }
   with_act_norm(act, norm, [&](auto a, auto n) {
     k_rows_reg<T1, T2, T3, decltype(n)::value, decltype(a)::value><<<grid, RR_WG, 0, s>>>(R);
   });
@@ -1804,14 +1917,16 @@ int lds_row_tile(const Layout& lo, void (*kernel)(Args), const char* api, const 
     snprintf(what, sizeof(what), "%s: nets too wide for the LDS row tile", api);
     return fail(-1, what);
   }
-  static bool lds_set = false;  // (one per Args type, i.e. per kernel)
-  if (!lds_set) {
+  static const void* lds_set[4] = {};  // (the kernels of this Args type that have the limit raised)
+  int slot = 0;
+  while (slot < 3 && lds_set[slot] && lds_set[slot] != (const void*)kernel) ++slot;
+  if (lds_set[slot] != (const void*)kernel) {
     const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       snprintf(what, sizeof(what), "hipFuncSetAttribute %s", name);
       return hip_fail(e, what);
     }
-    lds_set = true;
+    lds_set[slot] = (const void*)kernel;
   }
   return 0;
 }
@@ -1879,8 +1994,18 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
     for (int l = 0; l < n->n_layers; ++l)
       if (!n->gw[l] || !n->gb[l]) return fail(-1, "zbp_minibatch: null .grad buffer");
   }
+  // zbp_symmetry: on with any of its switches; then every table is there, and the workspace was sized and
+  // packed for the 2 B kernel rows (include/zbot_ppo.h, the workspace rule)
+  const zbp_symmetry& sy = batch->symmetry;
+  const bool sym = sy.augment || sy.mirror_loss || sy.loss_acc;
+  if (sym) {
+    if (!sy.obs_perm || !sy.obs_sign || !sy.critic_perm || !sy.critic_sign || !sy.act_perm || !sy.act_sign)
+      return fail(-1, "zbp_minibatch: symmetry on with a null table");
+    if (sy.ws_batch != 2 * B) return fail(-1, "zbp_minibatch: symmetry needs a workspace of 2 * batch rows (ws_batch)");
+  }
+  const int rows = sym ? 2 * B : B;  // kernel rows
   hipStream_t s = (hipStream_t)stream;
-  const Layout lo = make_layout(actor, critic, B);
+  const Layout lo = make_layout(actor, critic, rows);
 
   RowArgs R{};
   R.n[0] = lo.n[0];
@@ -1890,25 +2015,34 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   R.std_param = std_param;
   R.ws = ws;
   R.stats = lo.stats;
-  R.B = B;
+  R.B = rows;
+  if (sym) {
+    R.sym_inv_loss = 1.f / (float)(sy.augment ? 2 * B : B);
+    R.sym_grad = sy.mirror_loss ? sy.mirror_coef * 2.f / ((float)B * (float)batch->num_actions) : 0.f;
+    R.sym_part = lo.sym;
+  }
   size_t lds;
-  if (int rc = lds_row_tile(lo, k_rows, "zbp_minibatch", "k_rows", R.lds_x, &R.lds_dz, R.lds_out, &R.lds_red, &lds)) return rc;
+  if (int rc = lds_row_tile(lo, sym ? k_rows_sym : k_rows, "zbp_minibatch", sym ? "k_rows_sym" : "k_rows", R.lds_x, &R.lds_dz,
+                            R.lds_out, &R.lds_red, &lds))
+    return rc;
   // the register-resident row kernel for the shipped shapes (ZBP_ROWS=lds: the LDS one, for A/Bs)
-  const int shape = reg_shape(lo, B);
+  const int shape = reg_shape(lo, rows);
   const bool norm = batch->actor_norm.mean || batch->critic_norm.mean;
   if (shape == 1)
-    launch_rows_reg<16, 16, 8>(actor->activation, norm, 2 * (B / 64), s, R);
+    launch_rows_reg<16, 16, 8>(actor->activation, norm, sym, 2 * (rows / 64), s, R);
   else if (shape == 2)
-    launch_rows_reg<8, 8, 8>(actor->activation, norm, 2 * (B / 64), s, R);
+    launch_rows_reg<8, 8, 8>(actor->activation, norm, sym, 2 * (rows / 64), s, R);
+  else if (sym)
+    k_rows_sym<<<rows / TR, ROW_THREADS, lds, s>>>(R);
   else
-    k_rows<<<B / TR, ROW_THREADS, lds, s>>>(R);
+    k_rows<<<rows / TR, ROW_THREADS, lds, s>>>(R);
   if (int rc = launch_check("k_rows")) return rc;
 
   WgradArgs W{};
   W.n[0] = lo.n[0];
   W.n[1] = lo.n[1];
   W.tm = lo.tm;
-  W.batch = B;
+  W.batch = rows;
   W.ws = ws;
   W.part = lo.part;
   k_wgrad<<<lo.tm.blk0[2 * MAXL], 256, 0, s>>>(W);
@@ -1918,8 +2052,14 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   D.n[0] = lo.n[0];
   D.n[1] = lo.n[1];
   D.tm = lo.tm;
-  D.row_tiles = shape ? B / RR_TR : B / TR;
+  D.row_tiles = shape ? rows / RR_TR : rows / TR;
   D.batch = B;
+  if (sym) {
+    D.sym_samples = B;
+    D.sym_loss_rows = sy.augment ? 2 * B : B;
+    D.sym_part = lo.sym;
+    D.sym_acc = sy.loss_acc;
+  }
   D.num_actions = batch->num_actions;
   for (int k = 0; k < 2; ++k) {
     const zbp_net* n = k ? critic : actor;
@@ -1937,7 +2077,10 @@ int zbp_minibatch(const zbp_net* actor, const zbp_net* critic, const float* std_
   D.part = lo.part;
   D.rstats = lo.stats;
   D.norm2 = ws + lo.scratch;
-  k_reduce<<<lo.tm.wtiles + 1, RED_THREADS, 0, s>>>(D);
+  if (sym)
+    k_reduce_sym<<<lo.tm.wtiles + 1, RED_THREADS, 0, s>>>(D);
+  else
+    k_reduce<<<lo.tm.wtiles + 1, RED_THREADS, 0, s>>>(D);
   return launch_check("k_reduce");
 }
 

@@ -21,6 +21,18 @@ class RslRlPpoActorCriticCfg:
 
 
 @dataclass
+class RslRlSymmetryCfg:
+    """rsl_rl's symmetry option (IsaacLab ``RslRlSymmetryCfg``): augment every minibatch with its mirror
+    image and / or add ``mirror_loss_coeff`` times the mirror loss. ``data_augmentation_func``: rsl_rl's
+    ``(obs=None, actions=None, env=None) -> (obs, actions)``; a ``rl/symmetry.SignedPermutation`` runs on
+    the fused kernels, any other callable on the torch path."""
+    use_data_augmentation: bool = False
+    use_mirror_loss: bool = False
+    mirror_loss_coeff: float = 0.0
+    data_augmentation_func: object = None
+
+
+@dataclass
 class RslRlPpoAlgorithmCfg:
     class_name: str = "PPO"
     value_loss_coef: float = 1.0
@@ -35,6 +47,7 @@ class RslRlPpoAlgorithmCfg:
     lam: float = 0.95
     desired_kl: float = 0.01
     max_grad_norm: float = 1.0
+    symmetry_cfg: RslRlSymmetryCfg | None = None
 
 
 @dataclass

@@ -53,12 +53,20 @@ class ObsNorm(C.Structure):
                 ("eps", C.c_float), ("until", C.c_int64), ("dim", C.c_int32)]
 
 
+class Symmetry(C.Structure):
+    """zbp_symmetry: one mirror map's device tables and the switches (all zero: off)."""
+    _fields_ = [("obs_perm", C.c_void_p), ("obs_sign", C.c_void_p), ("critic_perm", C.c_void_p),
+                ("critic_sign", C.c_void_p), ("act_perm", C.c_void_p), ("act_sign", C.c_void_p),
+                ("augment", C.c_int32), ("mirror_loss", C.c_int32), ("mirror_coef", C.c_float),
+                ("ws_batch", C.c_int32), ("loss_acc", C.c_void_p)]
+
+
 class Batch(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("critic_obs", C.c_void_p), ("actions", C.c_void_p), ("values", C.c_void_p),
                 ("advantages", C.c_void_p), ("returns", C.c_void_p), ("log_prob", C.c_void_p), ("mu", C.c_void_p),
                 ("sigma", C.c_void_p), ("idx", C.c_void_p), ("idx_offset", C.c_int64), ("batch", C.c_int32),
                 ("obs_dim", C.c_int32), ("critic_obs_dim", C.c_int32), ("num_actions", C.c_int32),
-                ("actor_norm", ObsNorm), ("critic_norm", ObsNorm)]
+                ("actor_norm", ObsNorm), ("critic_norm", ObsNorm), ("symmetry", Symmetry)]
 
 
 class LossCfg(C.Structure):
@@ -180,10 +188,35 @@ def mlp_activation(seq: nn.Sequential) -> int:
     return activation_code(acts[0]) if acts else 0
 
 
-def supported(policy, batch: int) -> bool:
+_warned_symmetry = False
+
+
+def symmetry_supported(policy, symmetry) -> bool:
+    """Whether the kernels state this symmetry cfg (PPO.symmetry): none, or a ``SignedPermutation`` whose
+    dims are the policy's. Any other callable runs on the torch path, after a one-time warning."""
+    global _warned_symmetry
+    if symmetry is None:
+        return True
+    from .symmetry import SignedPermutation
+    func = symmetry["data_augmentation_func"]
+    la, lc = mlp_layers(policy.actor), mlp_layers(policy.critic)
+    if isinstance(func, SignedPermutation) and la and lc and func.matches(la[0].in_features, lc[0].in_features,
+                                                                            la[-1].out_features):
+        return True
+    if not _warned_symmetry:
+        import warnings
+        warnings.warn("symmetry_cfg: the fused PPO kernels take a SignedPermutation of the policy's dims as "
+                      "data_augmentation_func; this one runs on the torch path")
+        _warned_symmetry = True
+    return False
+
+
+def supported(policy, batch: int, symmetry=None) -> bool:
     """Whether the fused kernels cover this ActorCritic and minibatch size (MLPs of one of the rsl_rl
     activations, the same for actor and critic, <= 4 layers, inputs <= 32, hidden multiples of 32 up to
-    256, critic output 1, batch a multiple of 32, fp32 on a GPU)."""
+    256, critic output 1, batch a multiple of 32, fp32 on a GPU) and symmetry cfg (symmetry_supported)."""
+    if symmetry is not None:
+        return supported(policy, batch) and symmetry_supported(policy, symmetry)
     try:
         la, lc = mlp_layers(policy.actor), mlp_layers(policy.critic)
     except TypeError:
@@ -246,6 +279,10 @@ class FusedUpdate:
     def __init__(self, alg, batch: int):
         self.alg = alg
         self.batch = batch
+        # rsl_rl's symmetry option (PPO.symmetry; supported() has checked it): a minibatch is then 2 x batch
+        # kernel rows, which is what the workspace, zbp_pack, zbp_act and zbp_optimizer_step are told
+        self.symmetry = getattr(alg, "symmetry", None)
+        self.rows = 2 * batch if self.symmetry is not None else batch
         pol = alg.policy
         self.la, self.lc = mlp_layers(pol.actor), mlp_layers(pol.critic)
         self.log_std = int(getattr(pol, "noise_std_type", "scalar") == "log")
@@ -265,18 +302,37 @@ class FusedUpdate:
         self.na, self.nc = _net(self.la, act), _net(self.lc, act)
         self.noise = noise_param(pol)
         self.norm_a, self.norm_c = obs_norm(pol.actor_obs_normalizer), obs_norm(pol.critic_obs_normalizer)
-        n = lib().zbp_workspace_floats(C.byref(self.na), C.byref(self.nc), self.batch)
+        self.sym = self._symmetry()
+        n = lib().zbp_workspace_floats(C.byref(self.na), C.byref(self.nc), self.rows)
         if n < 0:
             msg = lib().zbp_last_error()
             raise ZbotError(f"zbp_workspace_floats: unsupported nets ({msg.decode() if msg else ''})")
         if getattr(self, "ws", None) is None or self.ws.numel() != n:
             self.ws = torch.zeros(int(n), device=self.noise.device)
 
+    def _symmetry(self) -> Symmetry:
+        """zbp_symmetry of the algorithm's cfg: the map's tables on the device (uploaded once, kept by the
+        map), the switches, and the algorithm's symmetry-loss accumulator."""
+        sy = Symmetry()
+        if self.symmetry is None:
+            return sy
+        func, dev = self.symmetry["data_augmentation_func"], self.noise.device
+        cdim = self.lc[0].in_features
+        self._sym_tables = [func.device_tables("obs", dev), func.device_tables("critic", dev, cdim),
+                            func.device_tables("actions", dev)]
+        (op, os_), (cp, cs), (ap, as_) = self._sym_tables
+        sy.obs_perm, sy.obs_sign, sy.critic_perm, sy.critic_sign = op.data_ptr(), os_.data_ptr(), cp.data_ptr(), cs.data_ptr()
+        sy.act_perm, sy.act_sign = ap.data_ptr(), as_.data_ptr()
+        sy.augment, sy.mirror_loss = int(self.symmetry["use_data_augmentation"]), int(self.symmetry["use_mirror_loss"])
+        sy.mirror_coef, sy.ws_batch = float(self.symmetry["mirror_loss_coeff"]), self.rows
+        sy.loss_acc = self.alg.symmetry_sum.data_ptr()
+        return sy
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.ws.device).cuda_stream)
 
     def pack(self) -> None:
-        _check(lib().zbp_pack(C.byref(self.na), C.byref(self.nc), _p(self.ws), self.batch, self._stream()), "zbp_pack")
+        _check(lib().zbp_pack(C.byref(self.na), C.byref(self.nc), _p(self.ws), self.rows, self._stream()), "zbp_pack")
 
     def minibatch(self, storage, indices: torch.Tensor, offset: int) -> torch.Tensor:
         """Gradients of minibatch rows indices[offset:offset + batch] into every .grad; returns the
@@ -291,6 +347,7 @@ class FusedUpdate:
         b.idx, b.idx_offset, b.batch = indices.data_ptr(), int(offset), self.batch
         b.obs_dim, b.critic_obs_dim, b.num_actions = obs.shape[-1], cobs.shape[-1], storage.actions.shape[-1]
         b.actor_norm, b.critic_norm = self.norm_a, self.norm_c  # (raw storage rows, normalized in the gather)
+        b.symmetry = self.sym
         _check(lib().zbp_minibatch(C.byref(self.na), C.byref(self.nc), _p(self.noise), _p(self.noise.grad), C.byref(b),
                                    C.byref(self.loss), _p(self.ws), _p(self.stats), self._stream()), "zbp_minibatch")
         return self.stats
@@ -349,7 +406,7 @@ class FusedUpdate:
         nfm = 1 if (grads_from_minibatch and self._norm_ok) else 0
         _check(lib().zbp_optimizer_step(C.byref(self._params), _p(alg.lr_t), _p(self.stats), _p(acc), float(dk),
                                         float(alg.max_grad_norm), float(b1), float(b2), float(g["eps"]),
-                                        C.byref(self.na), C.byref(self.nc), _p(self.ws), self.batch, nfm,
+                                        C.byref(self.na), C.byref(self.nc), _p(self.ws), self.rows, nfm,
                                         self._stream()),
                "zbp_optimizer_step")
 
@@ -388,7 +445,7 @@ class FusedUpdate:
         io.actor_norm, io.critic_norm = self.norm_a, self.norm_c
         io.log_std = self.log_std
         _check(lib().zbp_act(C.byref(self.na), C.byref(self.nc), _p(self.noise), C.byref(io), _p(self.ws),
-                             self.batch, self._stream()), "zbp_act")
+                             self.rows, self._stream()), "zbp_act")
         return self._act_out
 
     def env_post(self, storage, rewards: torch.Tensor, dones: torch.Tensor, time_outs, gamma: float,

@@ -12,6 +12,9 @@ this is a compatible restatement: same module names and tensor semantics, same c
 * ``PPO.update``: ``num_learning_epochs`` x ``num_mini_batches`` shuffled minibatches; adaptive LR
   from the Gaussian KL (desired_kl, x/÷1.5, bounded [1e-5, 1e-2]); clipped surrogate + clipped
   value loss - entropy bonus; global-norm gradient clipping; Adam.
+* ``symmetry_cfg`` (rsl_rl's symmetry option): data augmentation with a mirror map and / or the mirror
+  loss, for any ``data_augmentation_func``; a ``rl/symmetry.SignedPermutation`` also runs on the fused
+  kernels.
 * On a GPU the minibatches run on ``libzbot_ppo.so`` (``zbot_lab_amd/rl/fused.py``, hand-written fp32
   MFMA kernels: forward, loss, backward in four launches per minibatch; on one GPU the adaptive
   learning rate, clipping and Adam fused too) whenever the nets fit its limits; the torch autograd path
@@ -240,12 +243,32 @@ class RolloutStorage:
                 yield obs[b], cobs[b], act[b], val[b], adv[b], ret[b], lp[b], mu[b], sig[b]
 
 
+def _symmetry_cfg(cfg) -> dict | None:
+    """rsl_rl's symmetry_cfg as PPO keeps it, or None when there is none."""
+    if not cfg:
+        return None
+    cfg = dict(cfg)
+    func = cfg.get("data_augmentation_func")
+    if isinstance(func, str):  # rsl_rl / IsaacLab: "module:attribute"
+        import importlib
+        mod, _, attr = func.partition(":")
+        func = getattr(importlib.import_module(mod), attr)
+    if not callable(func):
+        raise ValueError("symmetry_cfg: data_augmentation_func must be a callable "
+                         "(obs=None, actions=None, env=None) -> (obs, actions)")
+    # (with neither switch rsl_rl still computes the symmetry loss, for the log only)
+    return {"use_data_augmentation": bool(cfg.get("use_data_augmentation", False)),
+            "use_mirror_loss": bool(cfg.get("use_mirror_loss", False)),
+            "mirror_loss_coeff": float(cfg.get("mirror_loss_coeff", 0.0)), "data_augmentation_func": func,
+            "_env": cfg.get("_env")}
+
+
 class PPO:
     def __init__(self, policy: ActorCritic, num_learning_epochs: int = 5, num_mini_batches: int = 4,
                  clip_param: float = 0.2, gamma: float = 0.99, lam: float = 0.95, value_loss_coef: float = 1.0,
                  entropy_coef: float = 0.005, learning_rate: float = 1e-3, max_grad_norm: float = 1.0,
                  use_clipped_value_loss: bool = True, schedule: str = "adaptive", desired_kl: float = 0.01,
-                 device="cpu", multi_gpu_cfg: dict | None = None, **_):
+                 device="cpu", multi_gpu_cfg: dict | None = None, symmetry_cfg: dict | None = None, **_):
         self.device = device
         self.policy = policy.to(device)
         # the learning rate lives on the device: the adaptive-KL rule updates it without a host
@@ -255,6 +278,10 @@ class PPO:
         self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=self.lr_t if on_gpu else learning_rate,
                                           fused=on_gpu or None, capturable=on_gpu)
         self.update_sums = torch.zeros(3, device=device)  # value, surrogate, entropy of the last update
+        # rsl_rl's symmetry option: {use_data_augmentation, use_mirror_loss, mirror_loss_coeff,
+        # data_augmentation_func (a callable, or "module:attribute")}; None: off
+        self.symmetry = _symmetry_cfg(symmetry_cfg)
+        self.symmetry_sum = torch.zeros(1, device=device)  # the symmetry loss summed over the last update's minibatches
         self.storage: RolloutStorage | None = None
         self.clip_param, self.gamma, self.lam = clip_param, gamma, lam
         self.num_learning_epochs, self.num_mini_batches = num_learning_epochs, num_mini_batches
@@ -358,7 +385,10 @@ class PPO:
     def update_stats(self) -> dict:
         n = self.num_learning_epochs * self.num_mini_batches
         m = (self.update_sums / n).tolist()
-        return {"value_function": m[0], "surrogate": m[1], "entropy": m[2]}
+        out = {"value_function": m[0], "surrogate": m[1], "entropy": m[2]}
+        if self.symmetry is not None:
+            out["symmetry"] = float(self.symmetry_sum) / n
+        return out
 
     def fused_update(self):
         """The libzbot_ppo driver for this policy and minibatch size, or None (CPU tensors, nets
@@ -366,7 +396,7 @@ class PPO:
         if self._fused is None and os.environ.get("ZBOT_PPO_FUSED", "1") != "0" and self.storage is not None:
             from . import fused
             mb = self.storage.num_envs * self.storage.num_transitions_per_env // self.num_mini_batches
-            if fused.supported(self.policy, mb):
+            if fused.supported(self.policy, mb, self.symmetry):
                 self._fused = fused.FusedUpdate(self, mb)
         return self._fused
 
@@ -382,46 +412,81 @@ class PPO:
         self._fused = None
         self._flat, self._seg_pre, self._seg_post = None, None, None
 
+    def minibatch_loss(self, mbt, adaptive: bool = True):
+        """rsl_rl's loss of one minibatch (a tuple of ``mini_batch_generator``) in the policy's precision:
+        (loss, KL mean or None, value loss, surrogate loss, entropy mean, symmetry loss or None). With
+        ``symmetry`` set: the augmented rows and the mirror loss as rsl_rl states them, for any
+        ``data_augmentation_func``."""
+        obs_b, cobs_b, act_b, target_values_b, adv_b, returns_b, old_lp_b, old_mu_b, old_sigma_b = mbt
+        sym = self.symmetry
+        n_orig = obs_b.shape[0]
+        if sym is not None and sym["use_data_augmentation"]:
+            # rsl_rl: the augmented rows (originals first) join the batch; a mirrored row keeps its
+            # original's old log-prob, target value, advantage and return
+            aug, act_b = sym["data_augmentation_func"](obs={"policy": obs_b, "critic": cobs_b}, actions=act_b,
+                                                       env=sym.get("_env"))
+            obs_b, cobs_b = aug["policy"], aug["critic"]
+            num_aug = obs_b.shape[0] // n_orig
+            old_lp_b, target_values_b = old_lp_b.repeat(num_aug, 1), target_values_b.repeat(num_aug, 1)
+            adv_b, returns_b = adv_b.repeat(num_aug, 1), returns_b.repeat(num_aug, 1)
+        # rsl_rl calls policy.act() here; the sampled actions are unused, so only the
+        # distribution is rebuilt (no random draw inside the update)
+        self.policy.update_distribution(obs_b)
+        lp_b = self.policy.get_actions_log_prob(act_b)
+        value_b = self.policy.evaluate(cobs_b)
+        # (the KL statistic and the entropy bonus: the original rows only)
+        mu_b, sigma_b = self.policy.action_mean[:n_orig], self.policy.action_std[:n_orig]
+        entropy_b = self.policy.entropy[:n_orig]
+
+        kl_mean = None
+        if adaptive:
+            with torch.no_grad():
+                kl = torch.sum(torch.log(sigma_b / old_sigma_b + 1e-5)
+                               + (old_sigma_b.square() + (old_mu_b - mu_b).square()) / (2.0 * sigma_b.square())
+                               - 0.5, dim=-1)
+                kl_mean = torch.mean(kl)
+
+        ratio = torch.exp(lp_b - torch.squeeze(old_lp_b))
+        surrogate = -torch.squeeze(adv_b) * ratio
+        surrogate_clipped = -torch.squeeze(adv_b) * torch.clamp(ratio, 1.0 - self.clip_param,
+                                                                1.0 + self.clip_param)
+        surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
+        if self.use_clipped_value_loss:
+            value_clipped = target_values_b + (value_b - target_values_b).clamp(-self.clip_param,
+                                                                                self.clip_param)
+            value_loss = torch.max((value_b - returns_b).pow(2), (value_clipped - returns_b).pow(2)).mean()
+        else:
+            value_loss = (returns_b - value_b).pow(2).mean()
+        loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_b.mean()
+        symmetry_loss = None
+        if sym is not None:
+            # rsl_rl's mirror loss: the policy's mean on the mirrored observations against the mirrored
+            # mean of the originals (detached: the gradient flows through the mirrored rows only)
+            func = sym["data_augmentation_func"]
+            if not sym["use_data_augmentation"]:
+                obs_b = func(obs={"policy": obs_b, "critic": cobs_b}, actions=None, env=sym.get("_env"))[0]["policy"]
+            mean_b = self.policy.act_inference(obs_b.detach())
+            _, target_b = func(obs=None, actions=mean_b[:n_orig], env=sym.get("_env"))
+            symmetry_loss = torch.nn.functional.mse_loss(mean_b[n_orig:], target_b.detach()[n_orig:])
+            if sym["use_mirror_loss"]:
+                loss = loss + sym["mirror_loss_coeff"] * symmetry_loss
+        return loss, kl_mean, value_loss, surrogate_loss, entropy_b.mean(), symmetry_loss
+
     def update_steps(self) -> None:
         """All minibatch updates with no host synchronisation (graph-capturable on a GPU), over the
         permutation in ``mb_indices`` (``draw_minibatch_indices`` first)."""
         sums = self.update_sums
         sums.zero_()
+        self.symmetry_sum.zero_()
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         f = self.fused_update()
         if f is not None:
             self._update_steps_fused(f, sums, adaptive)
             return
-        for (obs_b, cobs_b, act_b, target_values_b, adv_b, returns_b, old_lp_b, old_mu_b,
-             old_sigma_b) in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs,
-                                                               self.mb_indices):
-            # rsl_rl calls policy.act() here; the sampled actions are unused, so only the
-            # distribution is rebuilt (no random draw inside the update)
-            self.policy.update_distribution(obs_b)
-            lp_b = self.policy.get_actions_log_prob(act_b)
-            value_b = self.policy.evaluate(cobs_b)
-            mu_b, sigma_b, entropy_b = self.policy.action_mean, self.policy.action_std, self.policy.entropy
-
-            kl_mean = None
-            if adaptive:
-                with torch.no_grad():
-                    kl = torch.sum(torch.log(sigma_b / old_sigma_b + 1e-5)
-                                   + (old_sigma_b.square() + (old_mu_b - mu_b).square()) / (2.0 * sigma_b.square())
-                                   - 0.5, dim=-1)
-                    kl_mean = torch.mean(kl)
-
-            ratio = torch.exp(lp_b - torch.squeeze(old_lp_b))
-            surrogate = -torch.squeeze(adv_b) * ratio
-            surrogate_clipped = -torch.squeeze(adv_b) * torch.clamp(ratio, 1.0 - self.clip_param,
-                                                                    1.0 + self.clip_param)
-            surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
-            if self.use_clipped_value_loss:
-                value_clipped = target_values_b + (value_b - target_values_b).clamp(-self.clip_param,
-                                                                                    self.clip_param)
-                value_loss = torch.max((value_b - returns_b).pow(2), (value_clipped - returns_b).pow(2)).mean()
-            else:
-                value_loss = (returns_b - value_b).pow(2).mean()
-            loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_b.mean()
+        for mbt in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, self.mb_indices):
+            loss, kl_mean, value_loss, surrogate_loss, entropy_mean, symmetry_loss = self.minibatch_loss(mbt, adaptive)
+            if symmetry_loss is not None:
+                self.symmetry_sum += symmetry_loss.detach()
 
             self.optimizer.zero_grad(set_to_none=False)
             loss.backward()
@@ -431,7 +496,7 @@ class PPO:
             nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
             self.optimizer.step()
 
-            sums += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy_b.mean().detach()])
+            sums += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy_mean.detach()])
         # release the last minibatch's autograd graph: a live graph keeps its AccumulateGrad nodes,
         # which remember the stream they were created on, and a later HIP-graph capture of this
         # update would then synchronise with that (default) stream and break the capture

@@ -81,6 +81,8 @@ class OnPolicyRunner:
             warnings.warn("empirical_normalization is deprecated: set the policy's actor_obs_normalization / "
                           "critic_obs_normalization", DeprecationWarning, stacklevel=2)
             self.policy_cfg["actor_obs_normalization"] = self.policy_cfg["critic_obs_normalization"] = True
+        if self.alg_cfg.get("symmetry_cfg"):  # rsl_rl hands the env to the augmentation function
+            self.alg_cfg["symmetry_cfg"] = dict(self.alg_cfg["symmetry_cfg"], _env=env)
         policy = ActorCritic(num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
         self.alg = PPO(policy, device=self.device, multi_gpu_cfg=self.multi_gpu_cfg, **self.alg_cfg)
         self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
