@@ -201,7 +201,15 @@ int zbp_gae(const float* rewards, const float* dones, const float* values, const
  * (the env's input) and the storage slot of this step: observations, critic observations, actions,
  * values, log-probabilities, mu, sigma. Reads the workspace's weight images (zbp_pack must follow
  * every parameter change; zbp_optimizer_step re-packs itself). Replaces the ~30 torch kernels of a
- * policy step (runner._rollout). */
+ * policy step (runner._rollout).
+ *
+ * The in-kernel draw's stream key is (noise_seed << 32) ^ (draw counter << 12) ^ noise_step, 64 bits.
+ * It is injective -- distinct (seed, counter, step) triples draw from distinct streams -- for
+ * 0 <= noise_step < ZBP_NOISE_STEPS (4096) and a draw counter < 2^20 (packs / optimizer steps of one
+ * workspace). Outside that range triples alias: (c, step 4096) is (c ^ 1,
+ * step 0), and (seed s, counter 2^20 ^ c) is (s ^ 1, counter c). zbp_act refuses a noise_step outside
+ * the range (noise == NULL); the counter lives on the device and is not checked. */
+#define ZBP_NOISE_STEPS 4096
 typedef struct {
   const float* obs;         /* [rows][obs_dim] */
   const float* critic_obs;  /* [rows][critic_obs_dim] */
@@ -215,7 +223,7 @@ typedef struct {
   float* st_mu;             /* [rows][num_actions] out */
   float* st_sigma;          /* [rows][num_actions] out */
   int32_t rows, obs_dim, critic_obs_dim, num_actions;
-  int32_t noise_step;       /* (noise == NULL) the rollout step: distinct draws per step of a rollout */
+  int32_t noise_step;       /* (noise == NULL) the rollout step, in [0, ZBP_NOISE_STEPS): distinct draws per step */
   int32_t noise_seed;       /* (noise == NULL) the caller's stream, e.g. one per rank */
   zbp_obs_norm actor_norm;  /* the actor sees normalized obs (mean == NULL: none); st_obs stays raw */
   zbp_obs_norm critic_norm; /* the critic sees normalized critic_obs; st_critic_obs stays raw */

@@ -141,3 +141,28 @@ def test_create_rejects_weighted_term_without_active_bit():
     h = C.c_void_p()
     rc = L.zb_create(C.byref(mc), C.byref(c), 4, 0, 0, C.byref(h))
     assert rc < 0 and b"reward_active" in L.zb_last_error()
+
+
+def test_act_refuses_noise_step_outside_the_key_range():
+    """zbp_act with the in-kernel draw (noise NULL) refuses a noise_step outside [0, 4096) before any HIP
+    call: beyond it the step would alias the draw counter in the stream key (include/zbot_ppo.h)."""
+    from zbot_lab_amd.rl import fused
+    L = fused.lib()
+    n = fused.Net()
+    n.n_layers = 4
+    for i, dd in enumerate([23, 128, 128, 128, 6]):
+        n.dim[i] = dd
+    for i in range(4):
+        n.w[i] = n.b[i] = 16  # non-null; not dereferenced before the check
+    m = fused.Net.from_buffer_copy(n)
+    m.dim[4] = 1
+    io = fused.ActIO()
+    for f in ("obs", "critic_obs", "actions", "st_obs", "st_critic_obs", "st_actions", "st_values", "st_log_prob",
+              "st_mu", "st_sigma"):
+        setattr(io, f, 16)
+    io.noise = None
+    io.rows, io.obs_dim, io.critic_obs_dim, io.num_actions = 64, 23, 23, 6
+    for step in (4096, -1, 2 ** 31 - 1):
+        io.noise_step = step
+        rc = L.zbp_act(C.byref(n), C.byref(m), C.c_void_p(16), C.byref(io), C.c_void_p(16), 256, None)
+        assert rc < 0 and b"noise_step" in L.zbp_last_error(), step

@@ -2124,6 +2124,8 @@ int zbp_optimizer_step(const zbp_params* params, float* lr, const float* stats, 
   return do_pack(lo, actor, critic, ws, s, &T);
 }
 
+#define ZBP_STR_(x) #x
+#define ZBP_STR(x) ZBP_STR_(x)
 int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param, const zbp_act_io* io, float* ws,
             int32_t batch, void* stream) {
   if (const char* e = check_nets(actor, critic)) return fail(-1, e);
@@ -2136,6 +2138,9 @@ int zbp_act(const zbp_net* actor, const zbp_net* critic, const float* std_param,
     return fail(-1, "zbp_act: observation / action dims");
   if (const char* e = check_norm(&io->actor_norm, io->obs_dim)) return fail(-1, e);
   if (const char* e = check_norm(&io->critic_norm, io->critic_obs_dim)) return fail(-1, e);
+  // (noise_at packs the step into the key's low 12 bits: outside them it would alias the draw counter)
+  if (!io->noise && (io->noise_step < 0 || io->noise_step >= ZBP_NOISE_STEPS))
+    return fail(-1, "zbp_act: noise_step outside [0, " ZBP_STR(ZBP_NOISE_STEPS) ")");
   const Layout lo = make_layout(actor, critic, batch);
   ActArgs A{};
   A.n[0] = lo.n[0];
