@@ -27,6 +27,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "zbot.h"
 
 namespace {
@@ -3146,15 +3148,98 @@ struct FinArgs {
   float* user_acc;  // zb_set_log_accumulator: += this step's log values (float[ZB_LOG_LEN + ZB_LOG_COUNTS])
 };
 
+// State accessors of the kernels below (until their #undef after the last reset kernel): row f of
+// env i in the state array, in the LDS carry (carry_prefetch), in the epilogue staging row.
+#define ST(f) st[(size_t)(f) * N + i]
+#define CST(f) cst[f]
+#define OUT(f) q.stg(f)
+
 __device__ __forceinline__ void load_phys(const float* __restrict__ st, int N, int i, Phys& p) {
-#define LD(f) st[(size_t)(f) * N + i]
 #pragma unroll
-  for (int a = 0; a < 3; ++a) { p.pos[a] = LD(ZB_S_ROOT_POS + a); p.lv[a] = LD(ZB_S_ROOT_LINVEL + a); p.av[a] = LD(ZB_S_ROOT_ANGVEL + a); }
+  for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
 #pragma unroll
-  for (int a = 0; a < 4; ++a) p.quat[a] = LD(ZB_S_ROOT_QUAT + a);
+  for (int a = 0; a < 4; ++a) p.quat[a] = ST(ZB_S_ROOT_QUAT + a);
 #pragma unroll
-  for (int j = 0; j < ND; ++j) { p.jq[j] = LD(ZB_S_JOINT_POS + j); p.jqd[j] = LD(ZB_S_JOINT_VEL + j); }
-#undef LD
+  for (int j = 0; j < ND; ++j) { p.jq[j] = ST(ZB_S_JOINT_POS + j); p.jqd[j] = ST(ZB_S_JOINT_VEL + j); }
+}
+
+// ------------------------------------------------------------------------- step-kernel scaffolding
+// What the four step kernels (walking v2, stand-up, walking v4, manager) share, stated once. The
+// __shared__ array and the kOcc == 1 register claim stay in the __global__ functions.
+
+// _pre_physics_step of walking v2, stand-up and walking v4: the tanh action, p_delta integrated at
+// the joint speed limit and clamped to +-pi, the joint targets; kRate: the action_rate term against
+// the previous action (v2.py:502-507). pr is the kernel's Pre record (parked in LDS by the caller).
+template <int kPDelta, int kActions, bool kRate, typename P>
+__device__ __forceinline__ void pre_action(MP m, const zb_task_cfg& cfg, const float* __restrict__ st, int N, int i,
+                                           const float* __restrict__ act, int s, float step_dt, P& pr,
+                                           float target[ND]) {
+  if (kRate) pr.action_rate = 0.f;
+  float a_tanh[ND];
+  actions_tanh(act, i, s, a_tanh);
+#pragma unroll
+  for (int j = 0; j < ND; ++j) {
+    const float a_prev = kRate ? ST(kActions + j) : 0.f;
+    pr.a_now[j] = a_tanh[j];
+    pr.pdel[j] = clampf(ST(kPDelta + j) + PI_F * pr.a_now[j] * cfg.joint_speed_limit * step_dt, -PI_F, PI_F);
+    target[j] = pr.pdel[j] + m->default_joint_pos[j];
+    if (kRate) pr.action_rate += (pr.a_now[j] - a_prev) * (pr.a_now[j] - a_prev);
+  }
+}
+
+// After the substep loop: this lane's warm-cache row (returned) and the Pre record back from LDS.
+// The model and state pointers go through an empty asm, so the MDP's direct loads are not hoisted
+// above the physics (they would be held in registers across all substeps).
+template <typename P>
+__device__ __forceinline__ float after_substeps(MP& m, const Q& q, float* __restrict__& st, P& pr) {
+  m = opaque(m);
+  wave_sync();
+  const float wc_row = wc_extract(q);
+  pr = *reinterpret_cast<const P*>(&q.pre());
+  st = opaque_ptr(st);
+  return wc_row;
+}
+
+// fields zeroed by _reset_idx
+struct Live {
+  bool reset;
+  __device__ __forceinline__ float operator()(float v) const { return reset ? 0.f : v; }
+};
+
+__device__ __forceinline__ void store_wc_row(const Q& q, float* __restrict__ wc, int N, int i, bool reset, float wc_row) {
+  // (an opaque 32-bit index: the load's address is not kept across the physics in a 64-bit register)
+  unsigned wi = (unsigned)(q.s * N + i);
+  asm volatile("" : "+v"(wi));
+  wc[wi] = reset ? wc_invalid(q.s) : wc_row;
+}
+
+// the physics rows of the staging row (the writer lane)
+__device__ __forceinline__ void stage_phys(const Q& q, const Phys& p) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { OUT(ZB_S_ROOT_POS + a) = p.pos[a]; OUT(ZB_S_ROOT_LINVEL + a) = p.lv[a]; OUT(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) OUT(ZB_S_ROOT_QUAT + a) = p.quat[a];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) { OUT(ZB_S_JOINT_POS + j) = p.jq[j]; OUT(ZB_S_JOINT_VEL + j) = p.jqd[j]; }
+}
+
+// The end of a step kernel: inside its writer block the kernel closes the staging row (SD state
+// rows, OD observation entries, then reward / terminated / truncated: stage_result; a writer block
+// of its own here changes every kernel's code), then the wave stores the rows (step_finish).
+template <int SD, int OD>
+__device__ __forceinline__ void stage_result(const Q& q, float reward, bool terminated, bool time_out) {
+  OUT(SD + OD) = reward;
+  OUT(SD + OD + 1) = terminated ? 1.f : 0.f;
+  OUT(SD + OD + 2) = time_out ? 1.f : 0.f;
+}
+template <int SD, int OD>
+__device__ __forceinline__ void step_finish(const Q& q, int N,
+                                            float* __restrict__ st, float* __restrict__ obs, float* __restrict__ rew,
+                                            uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
+                                            int64_t* __restrict__ done, Stamps& sp) {
+  staged_store<SD, OD>(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, st, obs, rew, term, trunc, done);
+  sp.mark(8);
+  sp.flush();
 }
 
 // One policy step per lane. Live state across the 4 substeps is kept to the physics state, the
@@ -3178,7 +3263,6 @@ __device__ __forceinline__ void step_body(const zb_model* __restrict__ mg, const
   // the env's state row: lane s loads fields s, s+16, ... (one coalesced load per field group)
   Stamps sp;
   sp.begin();
-#define ST(f) st[(size_t)(f) * N + i]
   Phys p;
 #pragma unroll
   for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
@@ -3187,7 +3271,6 @@ __device__ __forceinline__ void step_body(const zb_model* __restrict__ mg, const
 #pragma unroll
   for (int j = 0; j < ND; ++j) { p.jq[j] = ST(ZB_S_JOINT_POS + j); p.jqd[j] = ST(ZB_S_JOINT_VEL + j); }
   const float* cst = carry_prefetch<ZB_STATE_DIM>(q, st, N, i);
-#define CST(f) cst[f]
 
   // _pre_physics_step (v2.py:276-287); _actions / p_delta are stored with the rest at the end
   // (one writer lane per env; the team holds identical values)
@@ -3197,17 +3280,7 @@ __device__ __forceinline__ void step_body(const zb_model* __restrict__ mg, const
   {
     // what the MDP needs after the physics is parked in LDS (Pre), not held in registers
     Pre pr;
-    pr.action_rate = 0.f;
-    float a_tanh[ND];
-    actions_tanh(act, i, q.s, a_tanh);
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const float a_prev = ST(ZB_S_ACTIONS + j);
-      pr.a_now[j] = a_tanh[j];
-      pr.pdel[j] = clampf(ST(ZB_S_P_DELTA + j) + PI_F * pr.a_now[j] * cfg.joint_speed_limit * step_dt, -PI_F, PI_F);
-      target[j] = pr.pdel[j] + m->default_joint_pos[j];
-      pr.action_rate += (pr.a_now[j] - a_prev) * (pr.a_now[j] - a_prev);   // v2.py:502-507
-    }
+    pre_action<ZB_S_P_DELTA, ZB_S_ACTIONS, true>(m, cfg, st, N, i, act, q.s, step_dt, pr, target);
 
     // the previous _get_observations cache (one-step lag, v2.py:315-345): the pre-step terms are
     // evaluated now, only what step_length / dones need is carried across the physics
@@ -3249,10 +3322,8 @@ __device__ __forceinline__ void step_body(const zb_model* __restrict__ mg, const
     sp.mark(7);
     sp.substep_end(k);
   }
-  m = opaque(m);
-  wave_sync();
-  const float wc_row = wc_extract(q);
-  const Pre pr = q.pre();
+  Pre pr;
+  const float wc_row = after_substeps(m, q, st, pr);
   const float(&a_now)[ND] = pr.a_now;
   const float(&pdel)[ND] = pr.pdel;
   const float(&r_pre)[5] = pr.r_pre;
@@ -3262,9 +3333,7 @@ __device__ __forceinline__ void step_body(const zb_model* __restrict__ mg, const
   const float r_action_rate = pr.action_rate;
 
   // MDP state of this env (the LDS carry, or every lane loads; one writer lane stores at the
-  // end). The state pointer goes through an empty asm so direct loads are not hoisted above the
-  // physics (they would be held in registers across all substeps).
-  st = opaque_ptr(st);
+  // end); after_substeps keeps the direct loads below the physics
   float air_cur[2], air_last[2], contact_t[2], con_last_unused[2] = {0.f, 0.f};
   float step_len[2], f_last0[2], down[2][3], sums0[ZB_NUM_REWARD_TERMS];
 #pragma unroll
@@ -3410,22 +3479,11 @@ __device__ __forceinline__ void step_body(const zb_model* __restrict__ mg, const
     obs_q[0] = dq.x; obs_q[1] = dq.y; obs_q[2] = dq.z; obs_q[3] = dq.w;
   }
   log_flush(q, lmask, acc);
-  {
-    // (an opaque 32-bit index: the load's address is not kept across the physics in a 64-bit register)
-    unsigned wi = (unsigned)(q.s * N + i);
-    asm volatile("" : "+v"(wi));
-    wc[wi] = reset ? wc_invalid(q.s) : wc_row;
-  }
+  store_wc_row(q, wc, N, i, reset, wc_row);
   sp.mark(12);
-#define OUT(f) q.stg(f)
   if (writer) {
-    auto live = [reset](float v) { return reset ? 0.f : v; };  // fields zeroed by _reset_idx
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { OUT(ZB_S_ROOT_POS + a) = p.pos[a]; OUT(ZB_S_ROOT_LINVEL + a) = p.lv[a]; OUT(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) OUT(ZB_S_ROOT_QUAT + a) = p.quat[a];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) { OUT(ZB_S_JOINT_POS + j) = p.jq[j]; OUT(ZB_S_JOINT_VEL + j) = p.jqd[j]; }
+    const Live live{reset};
+    stage_phys(q, p);
 #pragma unroll
     for (int j = 0; j < ND; ++j) { OUT(ZB_S_P_DELTA + j) = live(pdel[j]); OUT(ZB_S_ACTIONS + j) = live(a_now[j]); }
 #pragma unroll
@@ -3458,16 +3516,9 @@ __device__ __forceinline__ void step_body(const zb_model* __restrict__ mg, const
       o[16 + j] = live(a_now[j]);
     }
     o[22] = cfg.joint_speed_limit;
-    o[ZB_OBS_DIM] = reward;
-    o[ZB_OBS_DIM + 1] = died ? 1.f : 0.f;
-    o[ZB_OBS_DIM + 2] = time_out ? 1.f : 0.f;
+    stage_result<ZB_STATE_DIM, ZB_OBS_DIM>(q, reward, died, time_out);
   }
-  staged_store<ZB_STATE_DIM, ZB_OBS_DIM>(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, st, obs, rew, term, trunc, done);
-#undef OUT
-  sp.mark(8);
-  sp.flush();
-#undef ST
-#undef CST
+  step_finish<ZB_STATE_DIM, ZB_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
 }
 
 // kOcc (every step kernel): 2 = up to 256 registers (two waves per SIMD once a launch has more
@@ -3765,7 +3816,6 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_su_step_kernel(
   for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
   Stamps sp;
   sp.begin();
-#define ST(f) st[(size_t)(f) * N + i]
   Phys p;
 #pragma unroll
   for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
@@ -3784,14 +3834,7 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_su_step_kernel(
   float target[ND];
   {
     Pre pr;
-    float a_tanh[ND];
-    actions_tanh(act, i, q.s, a_tanh);
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      pr.a_now[j] = a_tanh[j];
-      pr.pdel[j] = clampf(ST(ZB_SU_P_DELTA + j) + PI_F * pr.a_now[j] * cfg.joint_speed_limit * step_dt, -PI_F, PI_F);
-      target[j] = pr.pdel[j] + m->default_joint_pos[j];
-    }
+    pre_action<ZB_SU_P_DELTA, ZB_SU_ACTIONS, false>(m, cfg, st, N, i, act, q.s, step_dt, pr, target);
     if (writer) q.pre() = pr;
   }
 
@@ -3802,11 +3845,8 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_su_step_kernel(
     substep<false, true, kTgs, kRefresh, kRf>(m, cfg, p, target, q, false, true, so, nullptr, nullptr, sp);
     sp.mark(7);
   }
-  m = opaque(m);
-  wave_sync();
-  const float wc_row = wc_extract(q);
-  const Pre pr = q.pre();
-  st = opaque_ptr(st);
+  Pre pr;
+  const float wc_row = after_substeps(m, q, st, pr);
   const float czl0 = ST(ZB_SU_CENTER_Z_LAST);
   const float ep_len = ST(ZB_SU_EP_LEN) + 1.f;
   float sums0[ZB_SU_NUM_REWARD_TERMS];
@@ -3905,22 +3945,11 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_su_step_kernel(
     qmul(p.quat, qrel, obs_q);
   }
   log_flush(q, lmask, acc);
-  {
-    // (an opaque 32-bit index: the load's address is not kept across the physics in a 64-bit register)
-    unsigned wi = (unsigned)(q.s * N + i);
-    asm volatile("" : "+v"(wi));
-    wc[wi] = reset ? wc_invalid(q.s) : wc_row;
-  }
+  store_wc_row(q, wc, N, i, reset, wc_row);
   sp.mark(12);
-#define OUT(f) q.stg(f)
   if (writer) {
-    auto live = [reset](float v) { return reset ? 0.f : v; };
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { OUT(ZB_S_ROOT_POS + a) = p.pos[a]; OUT(ZB_S_ROOT_LINVEL + a) = p.lv[a]; OUT(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) OUT(ZB_S_ROOT_QUAT + a) = p.quat[a];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) { OUT(ZB_S_JOINT_POS + j) = p.jq[j]; OUT(ZB_S_JOINT_VEL + j) = p.jqd[j]; }
+    const Live live{reset};
+    stage_phys(q, p);
 #pragma unroll
     for (int j = 0; j < ND; ++j) { OUT(ZB_SU_P_DELTA + j) = live(pr.pdel[j]); OUT(ZB_SU_ACTIONS + j) = live(pr.a_now[j]); }
     OUT(ZB_SU_CENTER_Z_LAST) = reset ? cfg.center_z_init : czl;
@@ -3937,15 +3966,9 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_su_step_kernel(
       o[10 + j] = p.jqd[j];
       o[16 + j] = live(pr.a_now[j]);
     }
-    q.stg(ZB_SU_LINK_MU + ZB_SU_OBS_DIM) = reward;
-    q.stg(ZB_SU_LINK_MU + ZB_SU_OBS_DIM + 1) = died ? 1.f : 0.f;
-    q.stg(ZB_SU_LINK_MU + ZB_SU_OBS_DIM + 2) = time_out ? 1.f : 0.f;
+    stage_result<ZB_SU_LINK_MU, ZB_SU_OBS_DIM>(q, reward, died, time_out);
   }
-  staged_store<ZB_SU_LINK_MU, ZB_SU_OBS_DIM>(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, st, obs, rew, term, trunc, done);
-#undef OUT
-  sp.mark(8);
-  sp.flush();
-#undef ST
+  step_finish<ZB_SU_LINK_MU, ZB_SU_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
 }
 
 // explicit resets (env_ids, or all when ids == nullptr): episode log into acc, then the reset
@@ -3958,7 +3981,6 @@ __global__ void zb_su_reset_kernel(const zb_model* __restrict__ mg, zb_task_cfg 
   if (t >= n) return;
   const int i = ids ? ids[t] : t;
   if (i < 0 || i >= N) return;
-#define ST(f) st[(size_t)(f) * N + i]
   const float step_dt = cfg.sim_dt * (float)cfg.decimation;
   const float dur = fmaxf(ST(ZB_SU_EP_LEN) * step_dt, step_dt);
 #pragma unroll
@@ -3979,7 +4001,6 @@ __global__ void zb_su_reset_kernel(const zb_model* __restrict__ mg, zb_task_cfg 
   ST(ZB_SU_EP_LEN) = 0.f;
 #pragma unroll
   for (int k = 0; k < ZB_SU_NUM_REWARD_TERMS; ++k) ST(ZB_SU_EP_SUMS + k) = 0.f;
-#undef ST
 }
 
 // the observation of env i's current state (standup.py:593-618) into the row o (out of line: obs_row)
@@ -4065,7 +4086,6 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_v4_step_kernel(
   for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
   Stamps sp;
   sp.begin();
-#define ST(f) st[(size_t)(f) * N + i]
   Phys p;
 #pragma unroll
   for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
@@ -4074,7 +4094,6 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_v4_step_kernel(
 #pragma unroll
   for (int j = 0; j < ND; ++j) { p.jq[j] = ST(ZB_S_JOINT_POS + j); p.jqd[j] = ST(ZB_S_JOINT_VEL + j); }
   const float* cst = carry_prefetch<ZB_V4_STATE_DIM>(q, st, N, i);
-#define CST(f) cst[f]
 
   // _pre_physics_step (v4.py:776-804, mode 1)
   const bool writer = q.s == 0;
@@ -4114,11 +4133,8 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_v4_step_kernel(
     sens_record(q, k, so);
     sp.mark(7);
   }
-  m = opaque(m);
-  wave_sync();
-  const float wc_row = wc_extract(q);
-  const PreV4 pr = pv;
-  st = opaque_ptr(st);
+  PreV4 pr;
+  const float wc_row = after_substeps(m, q, st, pr);
 
   // ContactSensor (history 3, updated every physics step; air / contact timers incl.
   // last_contact_time)
@@ -4326,16 +4342,10 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_v4_step_kernel(
     he_obs = atan2f(sn, cs);
   }
   log_flush(q, lmask, acc);
-  {
-    // (an opaque 32-bit index: the load's address is not kept across the physics in a 64-bit register)
-    unsigned wi = (unsigned)(q.s * N + i);
-    asm volatile("" : "+v"(wi));
-    wc[wi] = reset ? wc_invalid(q.s) : wc_row;
-  }
+  store_wc_row(q, wc, N, i, reset, wc_row);
   sp.mark(12);
-#define OUT(f) q.stg(f)
   if (writer) {
-    auto live = [reset](float v) { return reset ? 0.f : v; };
+    const Live live{reset};
 #pragma unroll
     for (int a = 0; a < 3; ++a) { OUT(ZB_S_ROOT_POS + a) = p.pos[a]; OUT(ZB_S_ROOT_LINVEL + a) = p.lv[a]; OUT(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
 #pragma unroll
@@ -4379,16 +4389,9 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_v4_step_kernel(
     }
     o[22] = cmd[0];
     o[23] = he_obs;
-    q.stg(ZB_V4_STATE_DIM + ZB_V4_OBS_DIM) = reward;
-    q.stg(ZB_V4_STATE_DIM + ZB_V4_OBS_DIM + 1) = died ? 1.f : 0.f;
-    q.stg(ZB_V4_STATE_DIM + ZB_V4_OBS_DIM + 2) = time_out ? 1.f : 0.f;
+    stage_result<ZB_V4_STATE_DIM, ZB_V4_OBS_DIM>(q, reward, died, time_out);
   }
-  staged_store<ZB_V4_STATE_DIM, ZB_V4_OBS_DIM>(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, st, obs, rew, term, trunc, done);
-#undef OUT
-  sp.mark(8);
-  sp.flush();
-#undef ST
-#undef CST
+  step_finish<ZB_V4_STATE_DIM, ZB_V4_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
 }
 
 // explicit resets / construction (init = 1 also draws the interval-event timers, as Isaac Lab's
@@ -4401,7 +4404,6 @@ __global__ void zb_v4_reset_kernel(const zb_model* __restrict__ mg, const float4
   if (t >= n) return;
   const int i = ids ? ids[t] : t;
   if (i < 0 || i >= N) return;
-#define ST(f) st[(size_t)(f) * N + i]
   const float step_dt = cfg.sim_dt * (float)cfg.decimation;
   if (!init) {
     const float dur = fmaxf(ST(ZB_V4_EP_LEN) * step_dt, step_dt);
@@ -4459,7 +4461,6 @@ __global__ void zb_v4_reset_kernel(const zb_model* __restrict__ mg, const float4
   ST(ZB_V4_EP_LEN) = 0.f;
 #pragma unroll
   for (int k = 0; k < ZB_V4_NUM_REWARD_TERMS; ++k) ST(ZB_V4_EP_SUMS + k) = 0.f;
-#undef ST
 }
 
 // the observation of env i's current state (v4.py _get_observations) into the row o (out of line: obs_row)
@@ -4564,7 +4565,6 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_m_step_kernel(
   for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
   Stamps sp;
   sp.begin();
-#define ST(f) st[(size_t)(f) * N + i]
   Phys p;
 #pragma unroll
   for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
@@ -4573,7 +4573,6 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_m_step_kernel(
 #pragma unroll
   for (int j = 0; j < ND; ++j) { p.jq[j] = ST(ZB_S_JOINT_POS + j); p.jqd[j] = ST(ZB_S_JOINT_VEL + j); }
   const float* cst = carry_prefetch<ZB_M_LINK_MU>(q, st, N, i);  // the friction rows load into FRIC
-#define CST(f) cst[f]
   if (q.s < NL) {
     q.fric(q.s) = ST(ZB_M_LINK_MU + q.s);
     q.fricd(q.s) = ST(ZB_M_LINK_MU_D + q.s);
@@ -4642,11 +4641,8 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_m_step_kernel(
     }
     sp.mark(7);
   }
-  m = opaque(m);
-  wave_sync();
-  const float wc_row = wc_extract(q);
-  const PreM pr = pv;
-  st = opaque_ptr(st);
+  PreM pr;
+  const float wc_row = after_substeps(m, q, st, pr);
 
   const float ep_len = CST(ZB_M_EP_LEN) + 1.f;
   float cmd[3] = {CST(ZB_M_COMMANDS), CST(ZB_M_COMMANDS + 1), CST(ZB_M_COMMANDS + 2)};
@@ -4837,22 +4833,11 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_m_step_kernel(
     if (standing > 0.5f) cmd[0] = cmd[1] = cmd[2] = 0.f;
   }
   log_flush(q, lmask, acc);
-  {
-    // (an opaque 32-bit index: the load's address is not kept across the physics in a 64-bit register)
-    unsigned wi = (unsigned)(q.s * N + i);
-    asm volatile("" : "+v"(wi));
-    wc[wi] = reset ? wc_invalid(q.s) : wc_row;
-  }
+  store_wc_row(q, wc, N, i, reset, wc_row);
   sp.mark(12);
-#define OUT(f) q.stg(f)
   if (writer) {
-    auto live = [reset](float v) { return reset ? 0.f : v; };
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { OUT(ZB_S_ROOT_POS + a) = p.pos[a]; OUT(ZB_S_ROOT_LINVEL + a) = p.lv[a]; OUT(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) OUT(ZB_S_ROOT_QUAT + a) = p.quat[a];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) { OUT(ZB_S_JOINT_POS + j) = p.jq[j]; OUT(ZB_S_JOINT_VEL + j) = p.jqd[j]; }
+    const Live live{reset};
+    stage_phys(q, p);
 #pragma unroll
     for (int a = 0; a < ND; ++a) OUT(ZB_M_ACTIONS + a) = a_obs[a];
 #pragma unroll
@@ -4876,16 +4861,9 @@ __global__ __launch_bounds__(WGT, kOcc) void zb_m_step_kernel(
 #pragma unroll
     for (int t = 0; t < ZB_M_NUM_REWARD_TERMS; ++t) OUT(ZB_M_EP_SUMS + t) = live(sums[t]);
     m_write_obs(m, cfg, hs, bq, cmd, p, a_obs, &q.stg(ZB_M_LINK_MU));
-    q.stg(ZB_M_LINK_MU + ZB_M_OBS_DIM) = reward;
-    q.stg(ZB_M_LINK_MU + ZB_M_OBS_DIM + 1) = terminated ? 1.f : 0.f;
-    q.stg(ZB_M_LINK_MU + ZB_M_OBS_DIM + 2) = time_out ? 1.f : 0.f;
+    stage_result<ZB_M_LINK_MU, ZB_M_OBS_DIM>(q, reward, terminated, time_out);
   }
-  staged_store<ZB_M_LINK_MU, ZB_M_OBS_DIM>(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, st, obs, rew, term, trunc, done);
-#undef OUT
-  sp.mark(8);
-  sp.flush();
-#undef ST
-#undef CST
+  step_finish<ZB_M_LINK_MU, ZB_M_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
 }
 
 // command of a reset env redrawn after lin_vel_cmd_levels widened the ranges (zb_finalize_kernel):
@@ -4919,7 +4897,6 @@ __global__ void zb_m_reset_kernel(const zb_model* __restrict__ mg, const float4*
   if (t >= n) return;
   const int i = ids ? ids[t] : t;
   if (i < 0 || i >= N) return;
-#define ST(f) st[(size_t)(f) * N + i]
   if (!init) {
 #pragma unroll
     for (int k = 0; k < ZB_M_NUM_REWARD_TERMS; ++k) atomicAdd(&acc_slot(acc, t)[k], ST(ZB_M_EP_SUMS + k));
@@ -4976,6 +4953,8 @@ __global__ void zb_m_reset_kernel(const zb_model* __restrict__ mg, const float4*
     for (int l = 0; l < NL; ++l) { ST(ZB_M_LINK_MU + l) = cfg.friction; ST(ZB_M_LINK_MU_D + l) = cfg.friction_dynamic; }
   }
 #undef ST
+#undef CST
+#undef OUT
 }
 
 // the observation of the current state (reset(): ObservationManager.compute after _reset_idx);
@@ -5318,6 +5297,92 @@ void zb_launch(F kernel, int blocks, hipStream_t s, hipEvent_t e0, hipEvent_t e1
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WGT), 0, s, args...);
 }
 
+// The task table: what the host side knows about each task, one row per ZB_TASK_*.
+struct TaskRow {
+  int state_dim, ep_row;  // state rows; the EP_LEN row (zb_finalize_kernel)
+  // episode-log divisor: walking v2 and the manager's RewardManager.reset divide the summed episode
+  // sums by the episode length (v2.py:446); stand-up and walking v4 already divided each env's sums
+  // by its own duration (standup.py:653-659)
+  bool log_per_episode;
+  int mu_row, mud_row;    // per-link friction rows (zb_set_link_friction_sd), or -1
+  bool four;              // has the <kTgs, kOcc, kRefresh, kRf> kernels (solver_modes 2, 3, self_manifold 3)
+  bool init_calls;        // the construction reset draws at RNG position 0; later calls start at 1
+  void (*critic)(zb_handle, float*, hipStream_t);
+  int (*init)(zb_handle);                                          // construction reset (checked inside)
+  void (*reset)(zb_handle, const int32_t*, int, hipStream_t, int);  // (ids, count, stream, init)
+  void (*observe)(zb_handle, float*, hipStream_t);
+};
+
+// the critic rows of the current state; the manager's policy block without its noise draw
+template <int kTask>
+static void critic_task(zb_handle h, float* dst, hipStream_t s) {
+  zb_task_cfg c = h->cfg;
+  if (kTask == ZB_TASK_MANAGER_V0) c.obs_corruption = 0;
+  zb_critic_obs_kernel<kTask><<<(h->n + CRIT_WG - 1) / CRIT_WG, CRIT_WG, 0, s>>>(h->d_model, c, h->n, h->d_state, h->inv_weight, dst);
+}
+
+static void reset_v2(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, int init) {
+  // construction: the spawn pose is the default pose, so the latch reads the default feet
+  zb_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->n, h->d_state, ids, cnt, h->d_acc,
+                                                    init ? 1 : h->cfg.reset_feet_refresh);
+}
+static void reset_su(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, int) {
+  zb_su_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, ids, cnt, h->d_acc, h->d_cnt,
+                                                       h->seed);
+}
+// construction (init = 1): reset events at RNG position 0 (+ interval timers)
+static void reset_v4(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, int init) {
+  zb_v4_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state, ids, cnt, h->d_acc,
+                                                       h->d_cnt, h->seed, init);
+}
+// construction (init = 1): ManagerBasedRLEnv.__init__ -> load_managers + reset events at RNG position 0
+// (friction default fill; the startup material event overwrites it)
+static void reset_m(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, int init) {
+  zb_m_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state, ids, cnt, h->d_acc,
+                                                      h->d_cnt, h->seed, init);
+}
+static int init_v2(zb_handle h) { reset_v2(h, nullptr, h->n, 0, 1); return launch_check("zb_reset_kernel"); }
+static int init_su(zb_handle h) {
+  const float fill[2] = {h->cfg.friction, h->cfg.friction_dynamic};
+  const int rows[2] = {ZB_SU_LINK_MU, ZB_SU_LINK_MU_D};
+  for (int k = 0; k < 2; ++k) {
+    zb_su_friction_kernel<<<(h->n * NL + 255) / 256, 256>>>(h->n, h->d_state, nullptr, fill[k], rows[k]);
+    const int rc = launch_check("zb_su_friction_kernel");
+    if (rc) return rc;
+  }
+  reset_su(h, nullptr, h->n, 0, 1);
+  return launch_check("zb_su_reset_kernel");
+}
+static int init_v4(zb_handle h) { reset_v4(h, nullptr, h->n, 0, 1); return launch_check("zb_v4_reset_kernel"); }
+static int init_m(zb_handle h) { reset_m(h, nullptr, h->n, 0, 1); return launch_check("zb_m_reset_kernel"); }
+
+static void observe_v2(zb_handle h, float* obs, hipStream_t s) {
+  zb_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->n, h->d_state, obs);
+}
+static void observe_su(zb_handle h, float* obs, hipStream_t s) {
+  zb_su_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->n, h->d_state, obs);
+}
+static void observe_v4(zb_handle h, float* obs, hipStream_t s) {
+  zb_v4_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->n, h->d_state, obs);
+}
+static void observe_m(zb_handle h, float* obs, hipStream_t s) {
+  zb_m_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, obs, h->d_cnt, h->seed);
+}
+
+static const TaskRow kTasks[] = {
+    /* ZB_TASK_WALKING_V2 */ {ZB_STATE_DIM, ZB_S_EP_LEN, true, -1, -1, true, false,
+                              critic_task<ZB_TASK_WALKING_V2>, init_v2, reset_v2, observe_v2},
+    /* ZB_TASK_STANDUP_V0 */ {ZB_SU_STATE_DIM, ZB_SU_EP_LEN, false, ZB_SU_LINK_MU, ZB_SU_LINK_MU_D, true, true,
+                              critic_task<ZB_TASK_STANDUP_V0>, init_su, reset_su, observe_su},
+    /* ZB_TASK_WALKING_V4 */ {ZB_V4_STATE_DIM, ZB_V4_EP_LEN, false, -1, -1, false, true,
+                              critic_task<ZB_TASK_WALKING_V4>, init_v4, reset_v4, observe_v4},
+    /* ZB_TASK_MANAGER_V0 */ {ZB_M_STATE_DIM, ZB_M_EP_LEN, true, ZB_M_LINK_MU, ZB_M_LINK_MU_D, false, true,
+                              critic_task<ZB_TASK_MANAGER_V0>, init_m, reset_m, observe_m},
+};
+constexpr int kNumTasks = sizeof(kTasks) / sizeof(kTasks[0]);
+static_assert(ZB_TASK_WALKING_V2 == 0 && ZB_TASK_STANDUP_V0 == 1 && ZB_TASK_WALKING_V4 == 2 && ZB_TASK_MANAGER_V0 == 3,
+              "kTasks row order");
+
 // The step-kernel instantiation of a handle: the template arguments <kTgs, kOcc, kRefresh, kRf> that
 // zb_step's dispatch selects and zb_kernel_variant reports (one place, so the two cannot disagree).
 // Walking v4 and the manager task have <kTgs, kOcc> kernels only (zb_create refuses solver_modes 2, 3
@@ -5329,8 +5394,25 @@ struct StepVariant {
 };
 
 static StepVariant step_variant(const zb_sim* h) {
-  const bool four = h->task != ZB_TASK_WALKING_V4 && h->task != ZB_TASK_MANAGER_V0;
+  const bool four = kTasks[h->task].four;
   return {h->cfg.solver_mode >= 1, h->occ1 ? 1 : 2, four && h->cfg.solver_mode >= 2, four && h->cfg.self_manifold == 3};
+}
+
+// f(kTgs, kOcc, kRefresh, kRf) with the variant's values as integral constants. kFour: the task has
+// the TGS refresh (always with kTgs) and the ruling-on-face builds; otherwise <kTgs, kOcc> only.
+template <bool kFour, typename F>
+static void with_variant(const StepVariant& v, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  auto occ = [&](auto tgs, auto refresh, auto rf) {
+    if (v.occ == 1) f(tgs, std::integral_constant<int, 1>{}, refresh, rf);
+    else f(tgs, std::integral_constant<int, 2>{}, refresh, rf);
+  };
+  if constexpr (kFour) {
+    if (v.refresh) return v.rf ? occ(T{}, T{}, T{}) : occ(T{}, T{}, N{});
+    if (v.rf) return v.tgs ? occ(T{}, N{}, T{}) : occ(N{}, N{}, T{});
+  }
+  return v.tgs ? occ(T{}, N{}, N{}) : occ(N{}, N{}, N{});
 }
 
 extern "C" {
@@ -5358,18 +5440,16 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
       }
     if (np != m->num_self_pairs) return set_err(-1, "zb_create: self-collision pair count", hipSuccess);
   }
+  const bool known = c->task >= 0 && c->task < kNumTasks && kTasks[c->task].init;
   if (c->decimation < 1 || c->decimation > MAXSUB || c->solver_iterations < 0 || c->solver_mode < 0 ||
       c->solver_mode > 3 || (c->solver_mode >= 1 && c->solver_iterations < 1) ||
-      (c->solver_mode >= 2 && c->task != ZB_TASK_WALKING_V2 && c->task != ZB_TASK_STANDUP_V0) ||
       c->self_manifold < 0 || c->self_manifold > 3 ||
-      (c->self_manifold == 3 && c->task != ZB_TASK_WALKING_V2 && c->task != ZB_TASK_STANDUP_V0))
+      (!(known && kTasks[c->task].four) && (c->solver_mode >= 2 || c->self_manifold == 3)))
     return set_err(-1, "zb_create: cfg (decimation 1..8, solver_iterations >= 0, solver_mode 0..3, iterations "
                        ">= 1 from mode 1; modes 2, 3 for walking v2 and stand-up; self_manifold 0..3, 3 for "
                        "walking v2 and stand-up)",
                    hipSuccess);
-  if (c->task != ZB_TASK_WALKING_V2 && c->task != ZB_TASK_STANDUP_V0 && c->task != ZB_TASK_WALKING_V4 &&
-      c->task != ZB_TASK_MANAGER_V0)
-    return set_err(-1, "zb_create: unknown task", hipSuccess);
+  if (!known) return set_err(-1, "zb_create: unknown task", hipSuccess);
   if (c->num_stages < 1 || c->num_stages > ZB_MAX_STAGES) return set_err(-1, "zb_create: num_stages", hipSuccess);
   if (c->task == ZB_TASK_WALKING_V2)  // a weighted term must be active (a zero-initialised reward_active would
     for (int t = 0; t < ZB_NUM_REWARD_TERMS; ++t)  // freeze its buffers silently; include/zbot.h)
@@ -5382,9 +5462,7 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
   h->n = num_envs;
   h->seed = seed;
   h->task = c->task;
-  h->state_dim = c->task == ZB_TASK_STANDUP_V0 ? ZB_SU_STATE_DIM
-                 : c->task == ZB_TASK_WALKING_V4 ? ZB_V4_STATE_DIM
-                 : c->task == ZB_TASK_MANAGER_V0 ? ZB_M_STATE_DIM : ZB_STATE_DIM;
+  h->state_dim = kTasks[c->task].state_dim;
   h->d_cnt = nullptr;
   h->cfg = *c;
   {
@@ -5491,45 +5569,12 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
   zb_derive_kernel<<<1, 1>>>(h->d_model, h->d_links);
   int rc = launch_check("zb_derive_kernel");
   if (rc) return rc;
-  if (h->task == ZB_TASK_STANDUP_V0) {
-    zb_su_friction_kernel<<<(num_envs * NL + 255) / 256, 256>>>(num_envs, h->d_state, nullptr, c->friction, ZB_SU_LINK_MU);
-    rc = launch_check("zb_su_friction_kernel");
-    if (rc) return rc;
-    zb_su_friction_kernel<<<(num_envs * NL + 255) / 256, 256>>>(num_envs, h->d_state, nullptr, c->friction_dynamic,
-                                                                ZB_SU_LINK_MU_D);
-    rc = launch_check("zb_su_friction_kernel");
-    if (rc) return rc;
-    // the construction-time reset draws its poses at RNG position 0; later calls start at 1
-    zb_su_reset_kernel<<<(num_envs + 255) / 256, 256>>>(h->d_model, h->cfg, num_envs, h->d_state, nullptr, num_envs,
-                                                       h->d_acc, h->d_cnt, h->seed);
-    rc = launch_check("zb_su_reset_kernel");
-    if (rc) return rc;
-    const uint64_t one = 1;
-    HIPCHK(hipMemcpy(&h->d_cnt->calls, &one, sizeof(one), hipMemcpyHostToDevice), "hipMemcpy counters");
-  } else if (h->task == ZB_TASK_WALKING_V4) {
-    // construction: reset events at RNG position 0 (+ interval timers); later calls start at 1
-    zb_v4_reset_kernel<<<(num_envs + 255) / 256, 256>>>(h->d_model, h->d_links, h->cfg, num_envs, h->d_state, nullptr,
-                                                       num_envs, h->d_acc, h->d_cnt, h->seed, 1);
-    rc = launch_check("zb_v4_reset_kernel");
-    if (rc) return rc;
-    const uint64_t one = 1;
-    HIPCHK(hipMemcpy(&h->d_cnt->calls, &one, sizeof(one), hipMemcpyHostToDevice), "hipMemcpy counters");
-  } else if (h->task == ZB_TASK_MANAGER_V0) {
-    // construction: ManagerBasedRLEnv.__init__ -> load_managers + reset events at RNG position 0
-    // (friction default fill; the startup material event overwrites it); later calls start at 1
-    zb_m_reset_kernel<<<(num_envs + 255) / 256, 256>>>(h->d_model, h->d_links, h->cfg, num_envs, h->d_state, nullptr,
-                                                      num_envs, h->d_acc, h->d_cnt, h->seed, 1);
-    rc = launch_check("zb_m_reset_kernel");
-    if (rc) return rc;
-    const uint64_t one = 1;
-    HIPCHK(hipMemcpy(&h->d_cnt->calls, &one, sizeof(one), hipMemcpyHostToDevice), "hipMemcpy counters");
-  } else {
-    // construction: the spawn pose is the default pose, so the latch reads the default feet
-    zb_reset_kernel<<<(num_envs + 255) / 256, 256>>>(h->d_model, h->d_links, num_envs, h->d_state, nullptr, num_envs,
-                                                      h->d_acc, 1);
-    rc = launch_check("zb_reset_kernel");
-  }
+  rc = kTasks[h->task].init(h);
   if (rc) return rc;
+  if (kTasks[h->task].init_calls) {
+    const uint64_t one = 1;
+    HIPCHK(hipMemcpy(&h->d_cnt->calls, &one, sizeof(one), hipMemcpyHostToDevice), "hipMemcpy counters");
+  }
   HIPCHK(hipMemset(h->d_acc, 0, sizeof(float) * ACC_SLOTS * ACC_STRIDE), "hipMemset acc");
   {
     HIPCHK(hipMalloc(&h->d_wc, sizeof(float) * ZB_WARM_ROWS * (size_t)num_envs), "hipMalloc contact cache");
@@ -5651,41 +5696,22 @@ void zb_destroy(zb_handle h) {
   delete h;
 }
 
-// episode-log divisor: walking divides the summed episode sums by the 20 s episode (v2.py:446),
-// standup already divided each env's sums by its own duration (standup.py:653-659)
 static float log_episode_s(zb_handle h) {
-  // (the manager's RewardManager.reset divides by max_episode_length_s too)
-  return h->task == ZB_TASK_WALKING_V2 || h->task == ZB_TASK_MANAGER_V0
-             ? h->cfg.sim_dt * h->cfg.decimation * h->cfg.max_episode_length
-             : 1.f;
+  return kTasks[h->task].log_per_episode ? h->cfg.sim_dt * h->cfg.decimation * h->cfg.max_episode_length : 1.f;
 }
 
 // the critic rows of the current state into dst (zb_observe_critic; after every step / reset while a
-// buffer is registered); the manager's policy block without its noise draw
+// buffer is registered)
 static int critic_obs(zb_handle h, float* dst, hipStream_t s) {
-  const int blocks = (h->n + CRIT_WG - 1) / CRIT_WG;
-  if (h->task == ZB_TASK_STANDUP_V0)
-    zb_critic_obs_kernel<ZB_TASK_STANDUP_V0><<<blocks, CRIT_WG, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, h->inv_weight, dst);
-  else if (h->task == ZB_TASK_WALKING_V4)
-    zb_critic_obs_kernel<ZB_TASK_WALKING_V4><<<blocks, CRIT_WG, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, h->inv_weight, dst);
-  else if (h->task == ZB_TASK_MANAGER_V0) {
-    zb_task_cfg clean = h->cfg;
-    clean.obs_corruption = 0;
-    zb_critic_obs_kernel<ZB_TASK_MANAGER_V0><<<blocks, CRIT_WG, 0, s>>>(h->d_model, clean, h->n, h->d_state, h->inv_weight, dst);
-  } else
-    zb_critic_obs_kernel<ZB_TASK_WALKING_V2><<<blocks, CRIT_WG, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, h->inv_weight, dst);
+  kTasks[h->task].critic(h, dst, s);
   return launch_check("zb_critic_obs_kernel");
 }
 
 static int finalize(zb_handle h, hipStream_t s, int full, int reset_counts, int is_step, float* obs = nullptr,
                     const uint8_t* term = nullptr, const uint8_t* trunc = nullptr) {
-  const int ep_row = h->task == ZB_TASK_STANDUP_V0   ? ZB_SU_EP_LEN
-                     : h->task == ZB_TASK_WALKING_V4 ? ZB_V4_EP_LEN
-                     : h->task == ZB_TASK_MANAGER_V0 ? ZB_M_EP_LEN
-                                                     : ZB_S_EP_LEN;
   zb_finalize_kernel<<<1, 256, 0, s>>>(h->n, h->d_state, h->d_acc, h->d_log_means, h->d_log_counts, h->u_log_means,
                                        h->u_log_counts, log_episode_s(h), h->seed, h->d_cnt, full, reset_counts, is_step,
-                                       ep_row, h->cfg, obs, term, trunc, h->u_log_acc);
+                                       kTasks[h->task].ep_row, h->cfg, obs, term, trunc, h->u_log_acc);
   return launch_check("zb_finalize_kernel");
 }
 
@@ -5694,18 +5720,7 @@ int zb_reset(zb_handle h, const int32_t* env_ids, int n, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int cnt = env_ids ? n : h->n;
   if (cnt <= 0) return 0;
-  if (h->task == ZB_TASK_STANDUP_V0)
-    zb_su_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, env_ids, cnt, h->d_acc,
-                                                         h->d_cnt, h->seed);
-  else if (h->task == ZB_TASK_WALKING_V4)
-    zb_v4_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state, env_ids, cnt,
-                                                         h->d_acc, h->d_cnt, h->seed, 0);
-  else if (h->task == ZB_TASK_MANAGER_V0)
-    zb_m_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state, env_ids, cnt,
-                                                        h->d_acc, h->d_cnt, h->seed, 0);
-  else
-    zb_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->n, h->d_state, env_ids, cnt, h->d_acc,
-                                                      h->cfg.reset_feet_refresh);
+  kTasks[h->task].reset(h, env_ids, cnt, s, 0);
   int rc = launch_check("zb_reset_kernel");
   if (rc) return rc;
   if (h->d_wc) {
@@ -5727,37 +5742,23 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
   const bool prof = h->prof_n < h->prof_max && (h->prof_seen++ % h->prof_stride) == 0;
   hipEvent_t e0 = prof ? h->prof_ev[2 * h->prof_n] : nullptr, e1 = prof ? h->prof_ev[2 * h->prof_n + 1] : nullptr;
   const StepVariant v = step_variant(h);
-  const bool tgs = v.tgs, refresh = v.refresh, one = v.occ == 1, rf = v.rf;
-#define ZB_LAUNCH(K, ...)                                                                          \
-  (tgs ? (one ? zb_launch(K<true, 1>, blocks, s, e0, e1, __VA_ARGS__) : zb_launch(K<true, 2>, blocks, s, e0, e1, __VA_ARGS__)) \
-       : (one ? zb_launch(K<false, 1>, blocks, s, e0, e1, __VA_ARGS__) : zb_launch(K<false, 2>, blocks, s, e0, e1, __VA_ARGS__)))
+  auto go = [&](auto kernel, auto... task_args) {
+    zb_launch(kernel, blocks, s, e0, e1, h->d_model, h->d_links, h->cfg, h->n, h->d_state, actions, obs, reward,
+              terminated, truncated, h->u_done, h->d_acc, task_args..., h->d_wc);
+  };
   // solver_modes 2, 3 (the TGS refresh) and self_manifold 3 (the ruling-on-face manifold): walking v2
   // and stand-up only (zb_create); one wave per SIMD at <= 4096 envs as the default kernels (round 6:
   // the refresh's FK and row rebuild inside the sweeps spill at two-wave occupancy)
-#define ZB_LAUNCH_R(K, ...)                                                                        \
-  (rf ? (refresh ? (one ? zb_launch(K<true, 1, true, true>, blocks, s, e0, e1, __VA_ARGS__)          \
-                        : zb_launch(K<true, 2, true, true>, blocks, s, e0, e1, __VA_ARGS__))         \
-                 : (tgs ? (one ? zb_launch(K<true, 1, false, true>, blocks, s, e0, e1, __VA_ARGS__)  \
-                               : zb_launch(K<true, 2, false, true>, blocks, s, e0, e1, __VA_ARGS__)) \
-                        : (one ? zb_launch(K<false, 1, false, true>, blocks, s, e0, e1, __VA_ARGS__) \
-                               : zb_launch(K<false, 2, false, true>, blocks, s, e0, e1, __VA_ARGS__)))) \
-      : refresh ? (one ? zb_launch(K<true, 1, true>, blocks, s, e0, e1, __VA_ARGS__)                 \
-                       : zb_launch(K<true, 2, true>, blocks, s, e0, e1, __VA_ARGS__))                \
-                : ZB_LAUNCH(K, __VA_ARGS__))
   if (h->task == ZB_TASK_STANDUP_V0)
-    ZB_LAUNCH_R(zb_su_step_kernel, h->d_model, h->d_links, h->cfg, h->n, h->d_state, actions, obs, reward, terminated,
-              truncated, h->u_done, h->d_acc, h->d_cnt, h->seed, h->d_wc);
+    with_variant<true>(v, [&](auto t, auto o, auto r, auto f) {
+      go(zb_su_step_kernel<t.value, o.value, r.value, f.value>, h->d_cnt, h->seed);
+    });
   else if (h->task == ZB_TASK_WALKING_V4)
-    ZB_LAUNCH(zb_v4_step_kernel, h->d_model, h->d_links, h->cfg, h->n, h->d_state, actions, obs, reward, terminated,
-              truncated, h->u_done, h->d_acc, h->d_cnt, h->seed, h->d_wc);
+    with_variant<false>(v, [&](auto t, auto o, auto, auto) { go(zb_v4_step_kernel<t.value, o.value>, h->d_cnt, h->seed); });
   else if (h->task == ZB_TASK_MANAGER_V0)
-    ZB_LAUNCH(zb_m_step_kernel, h->d_model, h->d_links, h->cfg, h->n, h->d_state, actions, obs, reward, terminated,
-              truncated, h->u_done, h->d_acc, h->d_cnt, h->seed, h->d_wc);
+    with_variant<false>(v, [&](auto t, auto o, auto, auto) { go(zb_m_step_kernel<t.value, o.value>, h->d_cnt, h->seed); });
   else
-    ZB_LAUNCH_R(zb_step_kernel, h->d_model, h->d_links, h->cfg, h->n, h->d_state, actions, obs, reward, terminated,
-              truncated, h->u_done, h->d_acc, h->d_wc);
-#undef ZB_LAUNCH_R
-#undef ZB_LAUNCH
+    with_variant<true>(v, [&](auto t, auto o, auto r, auto f) { go(zb_step_kernel<t.value, o.value, r.value, f.value>); });
   int rc = launch_check("zb_step_kernel");
   if (prof) ++h->prof_n;
   if (rc) return rc;
@@ -5769,15 +5770,7 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
 
 int zb_observe(zb_handle h, float* obs, void* stream) {
   if (!h || !obs) return set_err(-1, "zb_observe", hipSuccess);
-  if (h->task == ZB_TASK_STANDUP_V0)
-    zb_su_observe_kernel<<<(h->n + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->d_model, h->n, h->d_state, obs);
-  else if (h->task == ZB_TASK_WALKING_V4)
-    zb_v4_observe_kernel<<<(h->n + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->d_model, h->n, h->d_state, obs);
-  else if (h->task == ZB_TASK_MANAGER_V0)
-    zb_m_observe_kernel<<<(h->n + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->d_model, h->cfg, h->n, h->d_state, obs,
-                                                                             h->d_cnt, h->seed);
-  else
-    zb_observe_kernel<<<(h->n + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->d_model, h->n, h->d_state, obs);
+  kTasks[h->task].observe(h, obs, (hipStream_t)stream);
   return launch_check("zb_observe_kernel");
 }
 
@@ -5792,15 +5785,15 @@ int zb_state_dim(zb_handle h) { return h ? h->state_dim : -1; }
 
 int zb_set_link_friction_sd(zb_handle h, const float* mu_static, const float* mu_dynamic, void* stream) {
   if (!h || !mu_static || !mu_dynamic) return set_err(-1, "zb_set_link_friction_sd", hipSuccess);
-  if (h->task != ZB_TASK_STANDUP_V0 && h->task != ZB_TASK_MANAGER_V0)
+  const TaskRow& row = kTasks[h->task];
+  if (row.mu_row < 0)
     return set_err(-1, "zb_set_link_friction: per-link friction is a standup / manager task state", hipSuccess);
-  const bool mgr = h->task == ZB_TASK_MANAGER_V0;
   zb_su_friction_kernel<<<(h->n * NL + 255) / 256, 256, 0, (hipStream_t)stream>>>(
-      h->n, h->d_state, mu_static, 0.f, mgr ? ZB_M_LINK_MU : ZB_SU_LINK_MU);
+      h->n, h->d_state, mu_static, 0.f, row.mu_row);
   int rc = launch_check("zb_su_friction_kernel");
   if (rc) return rc;
   zb_su_friction_kernel<<<(h->n * NL + 255) / 256, 256, 0, (hipStream_t)stream>>>(
-      h->n, h->d_state, mu_dynamic, 0.f, mgr ? ZB_M_LINK_MU_D : ZB_SU_LINK_MU_D);
+      h->n, h->d_state, mu_dynamic, 0.f, row.mud_row);
   return launch_check("zb_su_friction_kernel");
 }
 
