@@ -475,6 +475,11 @@ int zb_pair_manifold_mode(const float* pairs, int n, float margin, int mode, flo
  * device-only entry points without an oracle mirror, declared in their own header. */
 #include "zbot_critic_obs.h"
 
+/* The manager task's interval push event and yaw / heading commands (zb_set_manager_events and the
+ * event-state accessors): configuration and per-env state beside zb_task_cfg and the state rows, which
+ * the oracle compiles against and which therefore do not change; declared in their own header. */
+#include "zbot_manager_events.h"
+
 #ifdef __cplusplus
 }
 #endif

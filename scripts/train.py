@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -63,9 +64,39 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--symmetry_mode", choices=("aug", "mirror", "both"), default="both",
                     help="with --symmetry: data augmentation, the mirror loss, or both")
     ap.add_argument("--mirror_loss_coeff", type=float, default=0.5, help="with --symmetry: the mirror loss's weight")
+    g = ap.add_argument_group("manager env events (zbot-6b-walking-m-*)")
+    g.add_argument("--push_robot", action="store_true", default=False,
+                   help="restore the base cfg's events.push_robot: push_by_setting_velocity every 10-15 s, x / y in +-0.5 m/s")
+    g.add_argument("--ang_vel_z", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="the base_velocity command's ang_vel_z range (ranges and limit_ranges), rad/s")
+    g.add_argument("--heading_command", action="store_true", default=False,
+                   help="heading_command=True with ranges.heading = (-pi, pi): the yaw command tracks a heading "
+                        "target, clipped to --ang_vel_z (default +-1.0 rad/s)")
     ap.add_argument("--env", action="append", default=[], metavar="PATH=VALUE",
                     help="env cfg override by dotted path, e.g. solver.iterations=8 (simulator ablations)")
     return ap
+
+
+def apply_manager_events(env_cfg, args) -> None:
+    """--push_robot / --ang_vel_z / --heading_command onto the manager env cfg; any other task refuses them."""
+    if not (args.push_robot or args.ang_vel_z is not None or args.heading_command):
+        return
+    from zbot_lab_amd.envs.manager_flat import EventTerm, Zbot6BFlatEnvCfg
+    if not isinstance(env_cfg, Zbot6BFlatEnvCfg):
+        raise SystemExit(f"--push_robot / --ang_vel_z / --heading_command are manager-env options (zbot-6b-walking-m-*), "
+                         f"not for {args.task}")
+    cmd = env_cfg.commands.base_velocity
+    if args.push_robot:  # zbotlab_env_cfg.py:253-258
+        env_cfg.events.push_robot = EventTerm("push_by_setting_velocity", "interval",
+                                              {"velocity_range": {"x": (-0.5, 0.5), "y": (-0.5, 0.5)}},
+                                              interval_range_s=(10.0, 15.0))
+    if args.heading_command:
+        cmd.heading_command = True
+        cmd.ranges.heading = (-math.pi, math.pi)
+    if args.ang_vel_z is not None or args.heading_command:
+        az = tuple(args.ang_vel_z) if args.ang_vel_z is not None else (-1.0, 1.0)
+        cmd.ranges.ang_vel_z = az
+        cmd.limit_ranges.ang_vel_z = az
 
 
 def update_rsl_rl_cfg(agent_cfg, args):
@@ -114,6 +145,7 @@ def main(argv=None) -> dict:
         env_cfg.reward_cfg = REWARD_CFGS[args.reward_cfg]
     if args.critic_obs:
         env_cfg.critic_observations = True
+    apply_manager_events(env_cfg, args)
     zbot_lab_amd.tasks.apply_env_overrides(env_cfg, args.env)
 
     rank, local_rank = 0, 0

@@ -71,7 +71,12 @@ def lib():
     L.zb_critic_obs_dim.argtypes = [P]
     L.zb_set_critic_obs_buffer.argtypes = [P, P]
     L.zb_observe_critic.argtypes = [P, P, P]
-    for name in EXPORTED_CRITIC_OBS:
+    L.zb_set_manager_events.argtypes = [P, C.POINTER(zm.ZbManagerEvents), P]
+    L.zb_manager_events_active.argtypes = [P]
+    L.zb_manager_event_state_dim.argtypes = [P]
+    L.zb_get_manager_event_state.argtypes = [P, P, P]
+    L.zb_set_manager_event_state.argtypes = [P, P, P]
+    for name in EXPORTED_CRITIC_OBS + EXPORTED_MANAGER_EVENTS:
         getattr(L, name).restype = C.c_int
     for name in ("zb_create", "zb_num_envs", "zb_reset", "zb_step", "zb_observe", "zb_kernel_variant", "zb_read_log", "zb_set_log_buffers", "zb_set_log_accumulator", "zb_set_done_buffer",
                  "zb_get_state", "zb_set_state", "zb_get_contact_cache", "zb_set_contact_cache", "zb_physics_substeps",
@@ -90,6 +95,9 @@ EXPORTED = ["zb_create", "zb_destroy", "zb_last_error", "zb_num_envs", "zb_reset
 
 # include/zbot_critic_obs.h: device-only entry points without an oracle mirror (EXPORTED is zbot.h's own list)
 EXPORTED_CRITIC_OBS = ["zb_critic_obs_dim", "zb_set_critic_obs_buffer", "zb_observe_critic"]
+# include/zbot_manager_events.h: the manager task's interval push and yaw / heading commands, likewise
+EXPORTED_MANAGER_EVENTS = ["zb_set_manager_events", "zb_manager_events_active", "zb_manager_event_state_dim",
+                           "zb_get_manager_event_state", "zb_set_manager_event_state"]
 
 
 def check(rc: int, what: str) -> None:

@@ -2024,15 +2024,21 @@ __device__ __forceinline__ void staged_store(const Q& q, int env0, int N, float*
 // lane s of team e loads rows CARRY0 + s + 16 k of env e, so one load instruction covers 16 rows x
 // the EPW envs of the wave. The epilogue then reads LDS instead of waiting on ~40 HBM loads issued
 // after the physics. Returns the env's carry row indexed by state row (valid for rows >= CARRY0).
-template <int SD>
-__device__ __forceinline__ const float* carry_prefetch(const Q& q, const float* __restrict__ st, int N, int i) {
-  static_assert(SD - CARRY0 <= CARRY_W, "carry width");
-  constexpr int K = (SD - CARRY0 + TL - 1) / TL;
+// XD > 0: the XD rows of a side buffer x (SoA [XD][N], the manager's event state) follow as carry
+// rows SD .. SD + XD - 1, in the same load batch.
+template <int SD, int XD = 0>
+__device__ __forceinline__ const float* carry_prefetch(const Q& q, const float* __restrict__ st, int N, int i,
+                                                       const float* __restrict__ x = nullptr) {
+  static_assert(SD + XD - CARRY0 <= CARRY_W, "carry width");
+  constexpr int K = (SD + XD - CARRY0 + TL - 1) / TL;
   float v[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int r = CARRY0 + q.s + TL * k;
-    v[k] = r < SD ? st[(size_t)r * N + i] : 0.f;
+    if (XD > 0 && CARRY0 + TL * (k + 1) > SD)
+      v[k] = r < SD ? st[(size_t)r * N + i] : r < SD + XD ? x[(size_t)(r - SD) * N + i] : 0.f;
+    else
+      v[k] = r < SD ? st[(size_t)r * N + i] : 0.f;
   }
   float* c = q.carry();
 #pragma unroll
@@ -3146,6 +3152,7 @@ struct FinArgs {
   Counters* cnt;
   int ep_len_row;
   float* user_acc;  // zb_set_log_accumulator: += this step's log values (float[ZB_LOG_LEN + ZB_LOG_COUNTS])
+  int m_keep_yaw;   // manager: the step ran with events (m_fixup_env keeps the ang z command)
 };
 
 // State accessors of the kernels below (until their #undef after the last reset kernel): row f of
@@ -4522,6 +4529,93 @@ __device__ __forceinline__ void m_resample(const zb_task_cfg& cfg, const Counter
 }
 constexpr int M_DRAW_RESET_CMD = 5, M_DRAW_CMD = 9, M_DRAW_NOISE = 16;  // reset_pose uses draws 1..4
 
+// ------------------------------------------------------------- interval push, yaw / heading commands
+// include/zbot_manager_events.h. The draws are new indices of the same per-env stream: the push timer
+// at a reset, {ang z, heading target, is-heading} at a reset and at the timer resample, the push
+// timer redrawn on a fire, the six push components.
+constexpr int M_DRAW_RESET_PUSH_T = 8, M_DRAW_RESET_YAW = 12, M_DRAW_YAW = 32, M_DRAW_PUSH_T = 35, M_DRAW_PUSH = 36;
+static_assert(M_DRAW_RESET_CMD + 3 <= M_DRAW_RESET_PUSH_T && M_DRAW_CMD + 3 <= M_DRAW_RESET_YAW &&
+              M_DRAW_RESET_YAW + 3 <= M_DRAW_NOISE && M_DRAW_NOISE + 4 + 2 * ND <= M_DRAW_YAW &&
+              M_DRAW_YAW + 3 <= M_DRAW_PUSH_T && M_DRAW_PUSH_T < M_DRAW_PUSH, "manager draw-index map (DESIGN.md §6)");
+
+// zb_m_events_step_kernel's extra arguments as one record: the configuration and the side buffer
+// (SoA [ZB_ME_STATE_DIM][N]); zb_m_step_kernel has an empty one.
+template <bool kEvents>
+struct MEv {};
+template <>
+struct MEv<true> {
+  zb_manager_events c;
+  float* st;
+};
+// the staging-row entries of the event state, after {reward, terminated, truncated}
+constexpr int M_STG_EV = ZB_M_LINK_MU + ZB_M_OBS_DIM + 3;
+static_assert(M_STG_EV + ZB_ME_STATE_DIM <= STG_LEN, "staging row");
+
+__device__ __forceinline__ float m_uniform(uint64_t h, int k, const float r[2]) { return draw(h, k) * (r[1] - r[0]) + r[0]; }
+
+// UniformVelocityCommand._resample_command, the part m_resample leaves at 0: ang z ~ U(ranges.ang_vel_z);
+// with heading_command the heading target ~ U(ranges.heading) and is_heading_env = u <= rel_heading_envs;
+// draws k0 .. k0 + 2
+__device__ __forceinline__ void m_resample_yaw(const zb_manager_events& ev, uint64_t h, int k0, float& ang_z,
+                                               float& target, float& is_heading) {
+  ang_z = m_uniform(h, k0, ev.cmd_ang_vel_z);
+  target = ev.heading_command ? m_uniform(h, k0 + 1, ev.cmd_heading) : 0.f;
+  is_heading = ev.heading_command && draw(h, k0 + 2) <= ev.cmd_rel_heading ? 1.f : 0.f;
+}
+
+// UniformVelocityCommand._update_command for a heading env: ang z from the heading error of the base
+// link's x axis (bq: the base link's world quaternion)
+__device__ __forceinline__ void m_heading_cmd(const zb_manager_events& ev, const float bq[4], float target,
+                                              float is_heading, float cmd[3]) {
+  if (ev.heading_command && is_heading > 0.5f) {
+    const float hw = atan2f(2.f * (bq[0] * bq[3] + bq[1] * bq[2]), 1.f - 2.f * (bq[2] * bq[2] + bq[3] * bq[3]));
+    cmd[2] = clampf(ev.heading_stiffness * wrap_to_pi(target - hw), ev.cmd_ang_vel_z[0], ev.cmd_ang_vel_z[1]);
+  }
+}
+
+// push_by_setting_velocity: (dv, dw) ~ U(push_velocity_range) added to the velocity of the articulation
+// root (the base link, zb_model.api_root_link) at its COM c, joint rates unchanged: one rigid velocity
+// field dv + dw x (x - c) over the whole robot, i.e. in the chain root's twist (linear part at
+// p.pos) av += dw, lv += dv - dw x (c - p.pos). Reads the published body frames of the current pose.
+__device__ __forceinline__ void m_push(MP m, const Q& q, const zb_manager_events& ev, uint64_t h, Phys& p) {
+  float d[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) d[k] = m_uniform(h, M_DRAW_PUSH + k, ev.push_velocity_range[k]);
+  const int l = m->api_root_link;
+  float R[9], pb[3], lc[3], c[3], wc[3];
+  read_frame(q, link_body(l), R, pb);
+  ldc(lc, m->link_com[l]);
+  mv3(R, lc, c);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) c[a] += pb[a];
+  cross3(d + 3, c, wc);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    p.av[a] += d[3 + a];
+    p.lv[a] += d[a] - wc[a];
+  }
+}
+
+// a reset env's event state (EventManager.reset: the push timer; the command term's reset: ang z, the
+// heading target and flag), one thread per env: zb_m_reset_kernel and zb_m_events_init_kernel
+__device__ __forceinline__ void m_reset_events(const zb_manager_events& evc, uint64_t hs, int N, int i,
+                                               float* __restrict__ ev, float& ang_z) {
+  float target, is_heading;
+  m_resample_yaw(evc, hs, M_DRAW_RESET_YAW, ang_z, target, is_heading);
+  ev[(size_t)ZB_ME_PUSH_TIME_LEFT * N + i] = evc.push_enabled ? m_uniform(hs, M_DRAW_RESET_PUSH_T, evc.push_interval_s) : 0.f;
+  ev[(size_t)ZB_ME_HEADING_TARGET * N + i] = target;
+  ev[(size_t)ZB_ME_IS_HEADING * N + i] = is_heading;
+}
+
+// the event-state entries of the staging row out to the side buffer: one store of the wave
+__device__ __forceinline__ void m_ev_store(const Q& q, int env0, int N, float* __restrict__ ev) {
+  wave_sync();
+  const float* S = reinterpret_cast<const float*>(q.b + YG_OFF);
+  const int e = q.lane % EPW, f0 = q.lane / EPW;
+  const int env = env0 + e;
+  if (env < N && f0 < ZB_ME_STATE_DIM) ev[(size_t)f0 * N + env] = S[e * STG_LEN + M_STG_EV + f0];
+}
+
 // the policy observation group (mgr.py:136-161, corruption on): root quat, command, joint pos rel,
 // joint vel rel (Isaac Lab joint order), last action; additive U(-n, n) noise from draws 16..37
 __device__ __forceinline__ void m_write_obs(MP m, const zb_task_cfg& cfg, uint64_t h, const float bq[4],
@@ -4548,335 +4642,40 @@ struct PreM {
 };
 static_assert(sizeof(PreM) <= 16 * PRE4, "PreM fits PRE4 granules");
 
-template <bool kTgs, int kOcc>
-__global__ __launch_bounds__(WGT, kOcc) void zb_m_step_kernel(
-    const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg, int N, float* __restrict__ st,
-    const float* __restrict__ act, float* __restrict__ obs, float* __restrict__ rew, uint8_t* __restrict__ term,
-    uint8_t* __restrict__ trunc, int64_t* __restrict__ done, float* __restrict__ acc,
-    const Counters* __restrict__ cnt, uint64_t seed, float* __restrict__ wc) {
-  MP m = to_mp(mg);
-  __shared__ float4 lds[LDS4];
-  if (kOcc == 1) asm volatile("" ::: "a255");  // (zb_step_kernel: kOcc)
-  const int lane = threadIdx.x;
-  const int env = xcd_block(blockIdx.x, gridDim.x) * EPW + lane / TL;
-  const int i = env < N ? env : N - 1;
-  const bool lead = env < N && lane % TL == 0;
-  const Q q = make_q(lds, lane, links);
-  for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
-  Stamps sp;
-  sp.begin();
-  Phys p;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) p.quat[a] = ST(ZB_S_ROOT_QUAT + a);
-#pragma unroll
-  for (int j = 0; j < ND; ++j) { p.jq[j] = ST(ZB_S_JOINT_POS + j); p.jqd[j] = ST(ZB_S_JOINT_VEL + j); }
-  const float* cst = carry_prefetch<ZB_M_LINK_MU>(q, st, N, i);  // the friction rows load into FRIC
-  if (q.s < NL) {
-    q.fric(q.s) = ST(ZB_M_LINK_MU + q.s);
-    q.fricd(q.s) = ST(ZB_M_LINK_MU_D + q.s);
-  }
-
-  // ActionManager.process_action: RelativeJointPositionAction (scale 0.04 pi, zero offset, clip
-  // +-0.04 pi) in the Isaac Lab joint order, mapped onto the chain's joints
-  const bool writer = q.s == 0;
-  const float step_dt = cfg.sim_dt * (float)cfg.decimation;
-  PreM& pv = *reinterpret_cast<PreM*>(&q.pre());
-  float delta[ND];
-  {
-    PreM pr;
-    pr.action_rate = 0.f;
-#pragma unroll
-    for (int a = 0; a < ND; ++a) {
-      pr.a_raw[a] = act[(size_t)i * ZB_ACT_DIM + a];
-      const float d = pr.a_raw[a] - ST(ZB_M_ACTIONS + a);
-      pr.action_rate += d * d;
-    }
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      float a = pr.a_raw[0];
-#pragma unroll
-      for (int b = 1; b < ND; ++b) a = m->api_joint_index[j] == b ? pr.a_raw[b] : a;
-      delta[j] = m->api_joint_sign[j] * clampf(a * cfg.action_scale, -cfg.action_clip, cfg.action_clip);
-      pr.jqd_prev[j] = 0.f;
-    }
-    if (writer) pv = pr;
-  }
-
-  // 4 x (apply_action: target = q + delta from the current joint positions; physics step;
-  // ContactSensor.update: feet net force into the 3-slot history, air-time timers + sim_dt).
-  // With 4 substeps the 3 history slots are this step's substeps 2..4.
-  SensorOut so;
-  float fz_h[3][2], fn_h[3][2];
-  float air_cur[2] = {ST(ZB_M_FEET_AIR_CUR), ST(ZB_M_FEET_AIR_CUR + 1)};
-  float air_last[2] = {ST(ZB_M_FEET_AIR_LAST), ST(ZB_M_FEET_AIR_LAST + 1)};
-  const bool hist_in = cfg.decimation < 3;  // >= 3 substeps overwrite every slot: no read
-#pragma unroll
-  for (int h = 0; h < 3; ++h)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      fz_h[h][f] = hist_in ? ST(ZB_M_FEET_FZ_HIST + 2 * h + f) : 0.f;
-      fn_h[h][f] = hist_in ? ST(ZB_M_FEET_FN_HIST + 2 * h + f) : 0.f;
-    }
-  wc_load(q, wc, N, i);  // the first substep's GJK warm start
-  sp.mark(0);
-  for (int k = 0; k < cfg.decimation; ++k) {
-    float target[ND];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) target[j] = p.jq[j] + delta[j];
-    if (k == cfg.decimation - 1 && writer) {
-#pragma unroll
-      for (int j = 0; j < ND; ++j) pv.jqd_prev[j] = p.jqd[j];
-    }
-    substep<false, true, kTgs>(m, cfg, p, target, q, true, true, so, nullptr, nullptr, sp);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const float fn = sqrtf(dot3(so.feet_f[f], so.feet_f[f]));
-      fz_h[2][f] = fz_h[1][f]; fz_h[1][f] = fz_h[0][f]; fz_h[0][f] = so.feet_f[f][2];
-      fn_h[2][f] = fn_h[1][f]; fn_h[1][f] = fn_h[0][f]; fn_h[0][f] = fn;
-      const bool c = fn > cfg.contact_force_threshold;
-      air_last[f] = (air_cur[f] > 0.f && c) ? air_cur[f] + cfg.sim_dt : air_last[f];
-      air_cur[f] = c ? 0.f : air_cur[f] + cfg.sim_dt;
-    }
-    sp.mark(7);
-  }
-  PreM pr;
-  const float wc_row = after_substeps(m, q, st, pr);
-
-  const float ep_len = CST(ZB_M_EP_LEN) + 1.f;
-  float cmd[3] = {CST(ZB_M_COMMANDS), CST(ZB_M_COMMANDS + 1), CST(ZB_M_COMMANDS + 2)};
-  float tleft = CST(ZB_M_CMD_TIME_LEFT), standing = CST(ZB_M_CMD_STANDING);
-  float met[2] = {CST(ZB_M_METRICS), CST(ZB_M_METRICS + 1)};
-  float f_last[2] = {CST(ZB_M_FEET_F_LAST), CST(ZB_M_FEET_F_LAST + 1)};
-  float step_len[2] = {CST(ZB_M_FEET_STEP_LEN), CST(ZB_M_FEET_STEP_LEN + 1)};
-  float down[2][3];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) down[f][a] = CST(ZB_M_FEET_DOWN_POS + 3 * f + a);
-
-  // post-step articulation data: root (= base link) pose, link-origin / COM velocity, angular
-  // velocity; feet link poses and COM velocities
-  float bq[4], bp[3], vb[3], vcom[3], wb[3], feet[2][3], fq[2][4], fvel[2][3];
-  {
-    wave_sync();
-    fk_team_pose(p, q);
-    wave_sync();
-    float S[ND][6], org[ND][3];
-    read_joints(q, S, org);
-    const int B = m->base_link;
-    link_pose_q(m, q, B, bp, bq);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) bp[a] += p.pos[a];
-    link_origin_vel_q(m, q, p, S, B, vb);
-    link_com_vel_q(m, q, p, S, B, vcom);
-    body_ang_vel_q(p, S, link_body(B), wb);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const int l = f == 0 ? 0 : 11;
-      link_pose_q(m, q, l, feet[f], fq[f]);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) feet[f][a] += p.pos[a];
-      link_com_vel_q(m, q, p, S, l, fvel[f]);
-    }
-  }
-  // TerminationManager (flat: time_out, base_height < 0.2, feet_close < 0.12)
-  const bool time_out = ep_len >= (float)cfg.max_episode_length;
-  const bool low = bp[2] < cfg.termination_height;
-  const float fd[3] = {feet[0][0] - feet[1][0], feet[0][1] - feet[1][1], feet[0][2] - feet[1][2]};
-  const bool close = sqrtf(dot3(fd, fd)) < cfg.feet_close_min;
-  const bool blowup = phys_bad(p);  // non-finite guard (phys_bad), as in the walking kernel
-  const bool terminated = low || close || blowup;
-
-  // RewardManager.compute: term * weight * step_dt in cfg order (mgr.py:262-357, flat overrides)
-  float r[ZB_M_NUM_REWARD_TERMS];
-  {
-    float Rb[9];
-    qmat(bq, Rb);
-    const float fwd[3] = {Rb[4], -Rb[1], 0.f};  // GRAVITY_VEC_W x quat_apply(root_quat, y)
-    float vx, vy;
-    {  // yaw_quat + quat_apply_inverse on root_link_lin_vel_w
-      const float yaw = atan2f(2.f * (bq[0] * bq[3] + bq[1] * bq[2]), 1.f - 2.f * (bq[2] * bq[2] + bq[3] * bq[3]));
-      float sy, cy;
-      sincos_r(yaw, &sy, &cy);
-      vx = cy * vb[0] + sy * vb[1];
-      vy = -sy * vb[0] + cy * vb[1];
-    }
-    const float ex = cmd[0] - vx, ey = cmd[1] - vy;
-    r[ZB_M_R_TRACK_LIN_VEL_XY] = __expf(-(ex * ex + ey * ey) / 0.25f);
-    const float ez = cmd[2] - wb[2];
-    r[ZB_M_R_TRACK_ANG_VEL_Z] = __expf(-(ez * ez) / 0.25f);
-    r[ZB_M_R_TERMINATION] = terminated ? 1.f : 0.f;
-    r[ZB_M_R_DOF_TORQUES] = so.tau2;
-    float ja = 0.f;
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const float aj = (p.jqd[j] - pr.jqd_prev[j]) / cfg.sim_dt;
-      ja += aj * aj;
-    }
-    r[ZB_M_R_DOF_ACC] = ja;
-    r[ZB_M_R_ACTION_RATE] = pr.action_rate;
-    // foot_step_length (rewards.py:44-104)
-    const float nrm = sqrtf(dot3(fwd, fwd)) + 1e-6f;
-    const float fh[3] = {fwd[0] / nrm, fwd[1] / nrm, fwd[2] / nrm};
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const float fz = (fz_h[0][f] + fz_h[1][f] + fz_h[2][f]) / 3.f;
-      if (fz > 10.f && f_last[f] < 10.f) {
-        const float dv[3] = {feet[f][0] - down[f][0], feet[f][1] - down[f][1], feet[f][2] - down[f][2]};
-        step_len[f] = fabsf(dot3(dv, fh));
-#pragma unroll
-        for (int a = 0; a < 3; ++a) down[f][a] = feet[f][a];
-      }
-      f_last[f] = fz;
-    }
-    r[ZB_M_R_FOOT_STEP_LENGTH] = tanh_r(15.f * fminf(step_len[0], step_len[1]));
-    float sd = 0.f, sfw = 0.f, sl = 0.f;
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      float R[9];
-      qmat(fq[f], R);
-      const float sg = f == 0 ? 1.f : -1.f;  // foot_downward: feet axes (0, 1, 0), (0, -1, 0) vs z
-      const float dz[3] = {sg * R[1], sg * R[4], sg * R[7] - 1.f};
-      sd += sqrtf(dot3(dz, dz));
-      const float dx[3] = {R[0] - fwd[0], R[3] - fwd[1], R[6] - fwd[2]};  // foot_forward
-      sfw += sqrtf(dot3(dx, dx));
-      const bool c = fmaxf(fn_h[0][f], fmaxf(fn_h[1][f], fn_h[2][f])) > 1.0f;  // feet_slide
-      sl += sqrtf(fvel[f][0] * fvel[f][0] + fvel[f][1] * fvel[f][1]) * (c ? 1.f : 0.f);
-    }
-    r[ZB_M_R_FOOT_DOWNWARD] = sd;
-    r[ZB_M_R_FOOT_FORWARD] = sfw;
-    r[ZB_M_R_FEET_SLIDE] = sl;
-    r[ZB_M_R_AIR_TIME_BALANCE] = fabsf(air_last[0] - air_last[1]);
-  }
-  float reward = 0.f, sums[ZB_M_NUM_REWARD_TERMS];
-#pragma unroll
-  for (int t = 0; t < ZB_M_NUM_REWARD_TERMS; ++t) {
-    const float v = r[t] * cfg.stage_scales[0][t] * step_dt;
-    reward += v;
-    sums[t] = CST(ZB_M_EP_SUMS + t) + v;
-  }
-  if (blowup) {  // finite reward (the is_terminated term alone), the episode sums without this step
-    reward = cfg.stage_scales[0][ZB_M_R_TERMINATION] * step_dt;
-#pragma unroll
-    for (int t = 0; t < ZB_M_NUM_REWARD_TERMS; ++t) sums[t] = CST(ZB_M_EP_SUMS + t);
-  }
-  const bool reset = terminated || time_out;
-  const uint64_t hs = env_hash(seed, cnt->calls, i);
-  float a_obs[ND];
-#pragma unroll
-  for (int a = 0; a < ND; ++a) a_obs[a] = pr.a_raw[a];
-  float vcb[3], wcb[3];  // root_lin_vel_b (COM), root_ang_vel_b after the resets
-
-  // _reset_idx: curriculum (finalize), events reset_base / reset_robot_joints / reset_my_data,
-  // managers (actions 0, reward sums and metrics logged, command resampled, sensor cleared)
-  const uint64_t lmask = __ballot(reset && lead);
-  if (reset) {
-    if (lead) {
-      float* lr = log_row(q);
-#pragma unroll
-      for (int t = 0; t < ZB_M_NUM_REWARD_TERMS; ++t) lr[t] = sums[t];
-      lr[ACC_NRES] = 1.f;
-      lr[ACC_DIED] = low ? 1.f : 0.f;
-      lr[ACC_TOUT] = time_out ? 1.f : 0.f;
-      lr[ACC_TERM2] = close ? 1.f : 0.f;
-      lr[ACC_MET0] = met[0];
-      lr[ACC_MET1] = met[1];
-    }
-    (void)reset_pose(m, cfg, hs, p);
-    const float4 qr = q.dflt()[3];
-    const float qrel[4] = {qr.x, qr.y, qr.z, qr.w};
-    qmul(p.quat, qrel, bq);
-    float R[9];
-    qmat(p.quat, R);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {  // reset_my_data: pre-reset feet (rewards.py:42) or reset pose's
-      const float4 fr = q.dflt()[4 + f];
-      const float v[3] = {fr.x, fr.y, fr.z};
-      float w3[3];
-      mv3(R, v, w3);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) down[f][a] = (cfg.reset_feet_refresh || blowup) ? p.pos[a] + w3[a] : feet[f][a];
-      f_last[f] = 0.f;
-      step_len[f] = 0.f;
-    }
-    m_resample(cfg, cnt, hs, M_DRAW_RESET_CMD, cmd, standing);
-    tleft = cfg.cmd_resample_s;
-    met[0] = met[1] = 0.f;
-#pragma unroll
-    for (int a = 0; a < ND; ++a) a_obs[a] = 0.f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { vcb[a] = 0.f; wcb[a] = 0.f; }
-  } else {
-    float R[9];
-    qmat(bq, R);
-    vcb[0] = R[0] * vcom[0] + R[3] * vcom[1] + R[6] * vcom[2];
-    vcb[1] = R[1] * vcom[0] + R[4] * vcom[1] + R[7] * vcom[2];
-    vcb[2] = R[2] * vcom[0] + R[5] * vcom[1] + R[8] * vcom[2];
-    wcb[0] = R[0] * wb[0] + R[3] * wb[1] + R[6] * wb[2];
-    wcb[1] = R[1] * wb[0] + R[4] * wb[1] + R[7] * wb[2];
-    wcb[2] = R[2] * wb[0] + R[5] * wb[1] + R[8] * wb[2];
-  }
-  // CommandManager.compute: metrics (UniformVelocityCommand._update_metrics), timer, resample,
-  // standing envs zeroed
-  {
-    const float max_steps = cfg.cmd_resample_s / step_dt;
-    const float ex = cmd[0] - vcb[0], ey = cmd[1] - vcb[1];
-    met[0] += sqrtf(ex * ex + ey * ey) / max_steps;
-    met[1] += fabsf(cmd[2] - wcb[2]) / max_steps;
-    tleft -= step_dt;
-    if (tleft <= 0.f) {
-      m_resample(cfg, cnt, hs, M_DRAW_CMD, cmd, standing);
-      tleft = cfg.cmd_resample_s;
-    }
-    if (standing > 0.5f) cmd[0] = cmd[1] = cmd[2] = 0.f;
-  }
-  log_flush(q, lmask, acc);
-  store_wc_row(q, wc, N, i, reset, wc_row);
-  sp.mark(12);
-  if (writer) {
-    const Live live{reset};
-    stage_phys(q, p);
-#pragma unroll
-    for (int a = 0; a < ND; ++a) OUT(ZB_M_ACTIONS + a) = a_obs[a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) OUT(ZB_M_COMMANDS + a) = cmd[a];
-    OUT(ZB_M_CMD_TIME_LEFT) = tleft;
-    OUT(ZB_M_CMD_STANDING) = standing;
-    OUT(ZB_M_METRICS) = met[0];
-    OUT(ZB_M_METRICS + 1) = met[1];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) OUT(ZB_M_FEET_DOWN_POS + 3 * f + a) = down[f][a];
-      OUT(ZB_M_FEET_STEP_LEN + f) = step_len[f];
-      OUT(ZB_M_FEET_F_LAST + f) = f_last[f];
-      OUT(ZB_M_FEET_AIR_CUR + f) = live(air_cur[f]);
-      OUT(ZB_M_FEET_AIR_LAST + f) = live(air_last[f]);
-#pragma unroll
-      for (int h = 0; h < 3; ++h) { OUT(ZB_M_FEET_FZ_HIST + 2 * h + f) = live(fz_h[h][f]); OUT(ZB_M_FEET_FN_HIST + 2 * h + f) = live(fn_h[h][f]); }
-    }
-    OUT(ZB_M_EP_LEN) = live(ep_len);
-#pragma unroll
-    for (int t = 0; t < ZB_M_NUM_REWARD_TERMS; ++t) OUT(ZB_M_EP_SUMS + t) = live(sums[t]);
-    m_write_obs(m, cfg, hs, bq, cmd, p, a_obs, &q.stg(ZB_M_LINK_MU));
-    stage_result<ZB_M_LINK_MU, ZB_M_OBS_DIM>(q, reward, terminated, time_out);
-  }
-  step_finish<ZB_M_LINK_MU, ZB_M_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
-}
+// zb_m_step_kernel and, with the events compiled in, zb_m_events_step_kernel: one text (zbot_m_step.inc)
+#define ZB_M_STEP_KERNEL zb_m_step_kernel
+#define ZB_M_EVENTS 0
+#define ZB_M_EV_PARAMS
+#define ZB_M_EV_INIT {}
+#include "zbot_m_step.inc"
+#undef ZB_M_STEP_KERNEL
+#undef ZB_M_EVENTS
+#undef ZB_M_EV_PARAMS
+#undef ZB_M_EV_INIT
+#define ZB_M_STEP_KERNEL zb_m_events_step_kernel
+#define ZB_M_EVENTS 1
+#define ZB_M_EV_PARAMS zb_manager_events evc, float* __restrict__ evst,
+#define ZB_M_EV_INIT {evc, evst}
+#include "zbot_m_step.inc"
+#undef ZB_M_STEP_KERNEL
+#undef ZB_M_EVENTS
+#undef ZB_M_EV_PARAMS
+#undef ZB_M_EV_INIT
 
 // command of a reset env redrawn after lin_vel_cmd_levels widened the ranges (zb_finalize_kernel):
 // the post-reset state has zero velocity, so the first metric update reads |command| only
 __device__ __forceinline__ void m_fixup_env(const zb_task_cfg& cfg, int N, float* __restrict__ st, float* __restrict__ obs,
-                                            const Counters* cnt, uint64_t hs, int i) {
+                                            const Counters* cnt, uint64_t hs, int i, int keep_yaw) {
   float cmd[3], standing;
   m_resample(cfg, cnt, hs, M_DRAW_RESET_CMD, cmd, standing);
   const float step_dt = cfg.sim_dt * (float)cfg.decimation;
   const float max_steps = cfg.cmd_resample_s / step_dt;
   const float ex = cmd[0] - 0.f, ey = cmd[1] - 0.f;
   st[(size_t)ZB_M_METRICS * N + i] = 0.f + sqrtf(ex * ex + ey * ey) / max_steps;
-  st[(size_t)(ZB_M_METRICS + 1) * N + i] = 0.f + fabsf(cmd[2] - 0.f) / max_steps;
+  // keep_yaw (zb_m_events_step_kernel ran): ang z has no curriculum, so the step kernel's yaw metric
+  // and its ang z command (drawn or heading-controlled, zeroed for a standing env) stand as they are
+  if (keep_yaw) cmd[2] = st[(size_t)(ZB_M_COMMANDS + 2) * N + i];
+  else st[(size_t)(ZB_M_METRICS + 1) * N + i] = 0.f + fabsf(cmd[2] - 0.f) / max_steps;
   st[(size_t)ZB_M_CMD_STANDING * N + i] = standing;
   if (standing > 0.5f) cmd[0] = cmd[1] = cmd[2] = 0.f;
 #pragma unroll
@@ -4891,7 +4690,8 @@ __device__ __forceinline__ void m_fixup_env(const zb_task_cfg& cfg, int N, float
 // CommandManager.compute, i.e. the next step).
 __global__ void zb_m_reset_kernel(const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg,
                                   int N, float* __restrict__ st, const int32_t* __restrict__ ids, int n,
-                                  float* __restrict__ acc, const Counters* __restrict__ cnt, uint64_t seed, int init) {
+                                  float* __restrict__ acc, const Counters* __restrict__ cnt, uint64_t seed, int init,
+                                  zb_manager_events evc, float* __restrict__ ev) {
   MP m = to_mp(mg);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
@@ -4916,6 +4716,7 @@ __global__ void zb_m_reset_kernel(const zb_model* __restrict__ mg, const float4*
   (void)reset_pose(m, cfg, hs, p);
   float cmd[3], standing;
   m_resample(cfg, cnt, hs, M_DRAW_RESET_CMD, cmd, standing);
+  if (ev) m_reset_events(evc, hs, N, i, ev, cmd[2]);  // (events on: include/zbot_manager_events.h)
 #pragma unroll
   for (int a = 0; a < 3; ++a) { ST(ZB_S_ROOT_POS + a) = p.pos[a]; ST(ZB_S_ROOT_LINVEL + a) = p.lv[a]; ST(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
 #pragma unroll
@@ -4982,6 +4783,17 @@ __global__ void zb_m_observe_kernel(const zb_model* __restrict__ mg, zb_task_cfg
   Phys p;
   load_phys(st, N, i, p);
   m_observe_row(m, cfg, env_hash(seed, cnt->calls, i), p, st, N, i, obs + (size_t)i * ZB_M_OBS_DIM);
+}
+
+// zb_set_manager_events: the event state of every env as a reset at the current stream position draws
+// it, and the drawn ang z into the command row (a standing env is zeroed by its next step, as after a reset)
+__global__ void zb_m_events_init_kernel(int N, float* __restrict__ st, const Counters* __restrict__ cnt, uint64_t seed,
+                                        zb_manager_events evc, float* __restrict__ ev) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  float ang_z;
+  m_reset_events(evc, env_hash(seed, cnt->calls, i), N, i, ev, ang_z);
+  st[(size_t)(ZB_M_COMMANDS + 2) * N + i] = ang_z;
 }
 
 // =========================================================================== critic observations
@@ -5208,7 +5020,7 @@ __device__ __forceinline__ void finalize_body(int N, float* __restrict__ st, flo
   // max_episode_length steps, so one workgroup does it)
   if (obs && cnt->changed)
     for (int i = threadIdx.x; i < N; i += blockDim.x)
-      if (term[i] || trunc[i]) m_fixup_env(cfg, N, st, obs, cnt, env_hash(seed, ctr, i), i);
+      if (term[i] || trunc[i]) m_fixup_env(cfg, N, st, obs, cnt, env_hash(seed, ctr, i), i, fa.m_keep_yaw);
   if (full && cfg.task != ZB_TASK_MANAGER_V0)  // ManagerBasedRLEnv has no full-reset draw
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
       const uint64_t h = hash64(seed ^ hash64(ctr * 0x100000001B3ull + (uint64_t)i));
@@ -5222,9 +5034,10 @@ __global__ void zb_finalize_kernel(int N, float* __restrict__ st, float* __restr
                                    uint64_t seed, Counters* __restrict__ cnt, int force_full, int reset_counts,
                                    int is_step, int ep_len_row, zb_task_cfg cfg, float* __restrict__ obs,
                                    const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc,
-                                   float* __restrict__ user_acc) {
+                                   float* __restrict__ user_acc, int m_keep_yaw) {
   __shared__ float sh[FIN_FG * ACC_STRIDE + ACC];
-  const FinArgs fa = {log_means, log_counts, user_means, user_counts, episode_s, seed, cnt, ep_len_row, user_acc};
+  const FinArgs fa = {log_means, log_counts, user_means, user_counts, episode_s, seed, cnt, ep_len_row, user_acc,
+                      m_keep_yaw};
   finalize_body(N, st, acc, fa, force_full, reset_counts, is_step, cfg, obs, term, trunc, sh);
 }
 
@@ -5265,6 +5078,11 @@ struct zb_sim {
   int prof_stride = 1, prof_seen = 0;  // time every prof_stride-th launch (zb_profile_stride)
   hipEvent_t* prof_ev = nullptr;
   bool occ1 = false;   // step kernels with one wave per SIMD (kOcc = 1; ZB_OCC1)
+  // manager task, include/zbot_manager_events.h: the configuration, the side buffer (ZB_ME_STATE_DIM x n,
+  // allocated by zb_create) and whether anything is enabled (the events kernel)
+  zb_manager_events ev = {};
+  float* d_ev = nullptr;
+  bool ev_on = false;
 };
 
 static thread_local char g_err[512] = "";
@@ -5339,7 +5157,7 @@ static void reset_v4(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, in
 // (friction default fill; the startup material event overwrites it)
 static void reset_m(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, int init) {
   zb_m_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state, ids, cnt, h->d_acc,
-                                                      h->d_cnt, h->seed, init);
+                                                      h->d_cnt, h->seed, init, h->ev, h->ev_on ? h->d_ev : nullptr);
 }
 static int init_v2(zb_handle h) { reset_v2(h, nullptr, h->n, 0, 1); return launch_check("zb_reset_kernel"); }
 static int init_su(zb_handle h) {
@@ -5582,6 +5400,10 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
     rc = launch_check("zb_wc_fill_kernel");
     if (rc) return rc;
   }
+  if (h->task == ZB_TASK_MANAGER_V0) {  // the event state (include/zbot_manager_events.h): zero while events are off
+    HIPCHK(hipMalloc(&h->d_ev, sizeof(float) * ZB_ME_STATE_DIM * (size_t)num_envs), "hipMalloc event state");
+    HIPCHK(hipMemset(h->d_ev, 0, sizeof(float) * ZB_ME_STATE_DIM * (size_t)num_envs), "hipMemset event state");
+  }
   HIPCHK(hipDeviceSynchronize(), "zb_create sync");
   *out = h;
   return 0;
@@ -5689,6 +5511,7 @@ void zb_destroy(zb_handle h) {
   (void)hipFree(h->d_links);
   (void)hipFree(h->d_state);
   (void)hipFree(h->d_wc);
+  (void)hipFree(h->d_ev);
   (void)hipFree(h->d_acc);
   (void)hipFree(h->d_cnt);
   (void)hipFree(h->d_log_means);
@@ -5711,7 +5534,7 @@ static int finalize(zb_handle h, hipStream_t s, int full, int reset_counts, int 
                     const uint8_t* term = nullptr, const uint8_t* trunc = nullptr) {
   zb_finalize_kernel<<<1, 256, 0, s>>>(h->n, h->d_state, h->d_acc, h->d_log_means, h->d_log_counts, h->u_log_means,
                                        h->u_log_counts, log_episode_s(h), h->seed, h->d_cnt, full, reset_counts, is_step,
-                                       kTasks[h->task].ep_row, h->cfg, obs, term, trunc, h->u_log_acc);
+                                       kTasks[h->task].ep_row, h->cfg, obs, term, trunc, h->u_log_acc, h->ev_on ? 1 : 0);
   return launch_check("zb_finalize_kernel");
 }
 
@@ -5756,7 +5579,10 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
   else if (h->task == ZB_TASK_WALKING_V4)
     with_variant<false>(v, [&](auto t, auto o, auto, auto) { go(zb_v4_step_kernel<t.value, o.value>, h->d_cnt, h->seed); });
   else if (h->task == ZB_TASK_MANAGER_V0)
-    with_variant<false>(v, [&](auto t, auto o, auto, auto) { go(zb_m_step_kernel<t.value, o.value>, h->d_cnt, h->seed); });
+    with_variant<false>(v, [&](auto t, auto o, auto, auto) {
+      if (h->ev_on) go(zb_m_events_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev);
+      else go(zb_m_step_kernel<t.value, o.value>, h->d_cnt, h->seed);
+    });
   else
     with_variant<true>(v, [&](auto t, auto o, auto r, auto f) { go(zb_step_kernel<t.value, o.value, r.value, f.value>); });
   int rc = launch_check("zb_step_kernel");
@@ -5840,6 +5666,43 @@ int zb_critic_obs_dim(zb_handle h) { return h ? critic_policy_dim(h->task) + ZB_
 int zb_set_critic_obs_buffer(zb_handle h, float* buf) {
   if (!h) return set_err(-1, "zb_set_critic_obs_buffer", hipSuccess);
   h->u_critic = buf;
+  return 0;
+}
+
+int zb_set_manager_events(zb_handle h, const zb_manager_events* ev, void* stream) {
+  if (!h || !ev) return set_err(-1, "zb_set_manager_events", hipSuccess);
+  if (h->task != ZB_TASK_MANAGER_V0)
+    return set_err(-1, "zb_set_manager_events: the interval push and yaw / heading commands are manager-task events", hipSuccess);
+  bool ok = ev->cmd_ang_vel_z[0] <= ev->cmd_ang_vel_z[1];
+  for (int k = 0; k < 6; ++k) ok = ok && ev->push_velocity_range[k][0] <= ev->push_velocity_range[k][1];
+  if (ev->push_enabled) ok = ok && ev->push_interval_s[0] > 0.f && ev->push_interval_s[0] <= ev->push_interval_s[1];
+  if (ev->heading_command) ok = ok && ev->cmd_heading[0] <= ev->cmd_heading[1];
+  if (!ok)
+    return set_err(-1, "zb_set_manager_events: every range needs lo <= hi (no NaN) and push_interval_s[0] > 0", hipSuccess);
+  h->ev = *ev;
+  h->ev_on = ev->push_enabled || ev->heading_command || ev->cmd_ang_vel_z[0] != 0.f || ev->cmd_ang_vel_z[1] != 0.f;
+  zb_m_events_init_kernel<<<(h->n + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->n, h->d_state, h->d_cnt, h->seed, h->ev,
+                                                                             h->d_ev);
+  return launch_check("zb_m_events_init_kernel");
+}
+
+int zb_manager_events_active(zb_handle h) { return h && h->ev_on ? 1 : 0; }
+
+int zb_manager_event_state_dim(zb_handle h) { return h && h->task == ZB_TASK_MANAGER_V0 ? ZB_ME_STATE_DIM : -1; }
+
+int zb_get_manager_event_state(zb_handle h, float* dst, void* stream) {
+  if (!h || !dst || !h->d_ev) return set_err(-1, "zb_get_manager_event_state (a manager-task handle)", hipSuccess);
+  HIPCHK(hipMemcpyAsync(dst, h->d_ev, sizeof(float) * ZB_ME_STATE_DIM * (size_t)h->n, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream),
+         "hipMemcpyAsync event state");
+  return 0;
+}
+
+int zb_set_manager_event_state(zb_handle h, const float* src, void* stream) {
+  if (!h || !src || !h->d_ev) return set_err(-1, "zb_set_manager_event_state (a manager-task handle)", hipSuccess);
+  HIPCHK(hipMemcpyAsync(h->d_ev, src, sizeof(float) * ZB_ME_STATE_DIM * (size_t)h->n, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream),
+         "hipMemcpyAsync event state");
   return 0;
 }
 

@@ -74,6 +74,7 @@ class UniformLevelVelocityCommandCfg:
     rel_standing_envs: float = 0.02
     rel_heading_envs: float = 1.0
     heading_command: bool = False
+    heading_control_stiffness: float = 1.0
     debug_vis: bool = True
     ranges: Ranges = field(default_factory=lambda: Ranges(lin_vel_x=(-0.1, 0.1)))
     limit_ranges: Ranges = field(default_factory=lambda: Ranges(lin_vel_x=(-0.3, 0.3)))
@@ -236,9 +237,7 @@ class Zbot6BFlatEnvCfg:
         if [k for k, _ in term] != zm.M_TERMINATION_TERMS:
             raise NotImplementedError(f"termination terms {[k for k, _ in term]} != {zm.M_TERMINATION_TERMS}")
         cmd = self.commands.base_velocity
-        if cmd.heading_command or tuple(cmd.ranges.ang_vel_z) != (0.0, 0.0) or \
-                tuple(cmd.limit_ranges.ang_vel_z) != (0.0, 0.0):
-            raise NotImplementedError("heading / angular-velocity commands are not compiled (flat cfg: 0)")
+        self.manager_events()  # push_robot, ang_vel_z, heading_command: raises on the forms not compiled
         lo, hi = cmd.resampling_time_range
         if lo != hi:
             raise NotImplementedError("resampling_time_range must be a single value (flat cfg: (10, 10))")
@@ -252,9 +251,10 @@ class Zbot6BFlatEnvCfg:
                 or any(n is not None and n[0] != -n[1] for n in noise):
             raise NotImplementedError("policy observation group: the compiled terms / symmetric noise only")
         ev = self.events
-        for k in ("add_base_mass", "base_com", "push_robot"):
+        for k in ("add_base_mass", "base_com"):
             if getattr(ev, k) is not None:
-                raise NotImplementedError(f"event {k} is not compiled (the flat cfg removes it)")
+                raise NotImplementedError(f"event {k} is not compiled (the flat cfg removes it): a per-env base "
+                                          "inertia reaches into the articulated-body pass of every step kernel")
         pr = ev.reset_base.params["pose_range"]
         if any(pr.get(k, (0.0, 0.0)) != (0.0, 0.0) for k in ("z", "pitch")) or \
                 any(tuple(v) != (0.0, 0.0) for v in ev.reset_base.params["velocity_range"].values()):
@@ -282,6 +282,46 @@ class Zbot6BFlatEnvCfg:
             obs_noise=tuple(0.0 if n is None else float(n[1]) for n in noise),
             range_period_steps=None if self.curriculum.lin_vel_cmd_levels is not None else -1,
         )
+
+
+    def manager_events(self) -> zm.ManagerEvents:
+        """Compile ``events.push_robot`` and the ``base_velocity`` command's ``ang_vel_z`` /
+        ``heading_command`` into the kernel's event parameters (``zb_set_manager_events``; they live beside
+        ``TaskCfg``, which they leave unchanged). The unedited cfg gives "events off". Raises
+        ``NotImplementedError`` on a form that is not compiled, saying what is."""
+        out = zm.ManagerEvents()
+        push = self.events.push_robot
+        if push is not None:
+            vr = push.params.get("velocity_range") if isinstance(push.params, dict) else None
+            if push.func != "push_by_setting_velocity" or push.mode != "interval" or push.interval_range_s is None \
+                    or not isinstance(vr, dict) or set(push.params) != {"velocity_range"} or not set(vr) <= set(zm.PUSH_AXES):
+                raise NotImplementedError(
+                    "events.push_robot: compiled as EventTerm('push_by_setting_velocity', 'interval', "
+                    "{'velocity_range': {x / y / z / roll / pitch / yaw: (lo, hi)}}, interval_range_s=(lo, hi)) "
+                    "with 0 < lo <= hi")
+            ilo, ihi = (float(v) for v in push.interval_range_s)
+            rng = tuple(tuple(float(v) for v in vr.get(k, (0.0, 0.0))) for k in zm.PUSH_AXES)
+            if not 0.0 < ilo <= ihi or any(a > b for a, b in rng):
+                raise NotImplementedError("events.push_robot: interval_range_s needs 0 < lo <= hi, every "
+                                          "velocity range lo <= hi")
+            out.push_enabled, out.push_interval_s, out.push_velocity_range = True, (ilo, ihi), rng
+        cmd = self.commands.base_velocity
+        az = tuple(float(v) for v in cmd.ranges.ang_vel_z)
+        if az != tuple(float(v) for v in cmd.limit_ranges.ang_vel_z) or az[0] > az[1]:
+            raise NotImplementedError("ranges.ang_vel_z must equal limit_ranges.ang_vel_z (lo <= hi): there is no "
+                                      "curriculum on the yaw command (ang_vel_cmd_levels is not in CurriculumCfg)")
+        out.cmd_ang_vel_z = az
+        if cmd.heading_command:
+            if cmd.ranges.heading is None:
+                raise NotImplementedError("heading_command=True needs ranges.heading=(lo, hi), and an "
+                                          "ang_vel_z range for the controller's output to be clipped to")
+            hd = tuple(float(v) for v in cmd.ranges.heading)
+            if hd[0] > hd[1]:
+                raise NotImplementedError("ranges.heading needs lo <= hi")
+            out.heading_command, out.cmd_heading = True, hd
+            out.cmd_rel_heading = float(cmd.rel_heading_envs)
+            out.heading_stiffness = float(cmd.heading_control_stiffness)
+        return out
 
 
 @dataclass
@@ -316,7 +356,40 @@ class _CommandManager:
     def get_term(self, name: str):
         if name != "base_velocity":
             raise KeyError(name)
-        return self._env.cfg.commands.base_velocity
+        return _VelocityCommandTerm(self._env)
+
+
+class _VelocityCommandTerm:
+    """The ``base_velocity`` command term: its cfg's fields (``ranges``, ``limit_ranges``, ...) and the
+    per-env buffers UniformVelocityCommand exposes (``command``, ``heading_target``, ``is_heading_env``)."""
+
+    def __init__(self, env: "ZbotManagerBasedRLEnv"):
+        object.__setattr__(self, "_env", env)
+        object.__setattr__(self, "cfg", env.cfg.commands.base_velocity)
+
+    def __getattr__(self, name: str):
+        return getattr(self.cfg, name)
+
+    def __setattr__(self, name: str, value) -> None:  # the term's fields are the cfg's: writes reach it too
+        setattr(self.cfg, name, value)
+
+    @property
+    def command(self) -> torch.Tensor:
+        return self._env.command_manager.get_command("base_velocity")
+
+    def _event_row(self, row: int) -> torch.Tensor:
+        sim = self._env.sim
+        if not sim.events_configured:  # events off: UniformVelocityCommand's zero-initialised buffers
+            return torch.zeros(sim.num_envs, dtype=torch.float32, device=sim.device)
+        return sim.get_event_state()[row].contiguous()
+
+    @property
+    def heading_target(self) -> torch.Tensor:
+        return self._event_row(zm.ME["HEADING_TARGET"])
+
+    @property
+    def is_heading_env(self) -> torch.Tensor:
+        return self._event_row(zm.ME["IS_HEADING"]) > 0.5
 
 
 class ZbotManagerBasedRLEnv(ZbotDirectEnvV2):
@@ -334,6 +407,9 @@ class ZbotManagerBasedRLEnv(ZbotDirectEnvV2):
         """Startup events: init_my_data (the feet buffers live in the state rows) and
         randomize_rigid_body_material over every body shape (64 buckets of static / dynamic
         friction ~ U[0.3, 1.0]; static and dynamic coefficients go to the solver)."""
+        events = self.cfg.manager_events()
+        if events.enabled:  # right after construction, before the first reset: construction semantics
+            self.sim.set_manager_events(events)
         ev = self.cfg.events.physics_material
         if ev is None:
             return

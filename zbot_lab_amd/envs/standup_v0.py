@@ -30,6 +30,7 @@ class EventTermCfg:
     func: str
     mode: str
     params: dict = field(default_factory=dict)
+    interval_range_s: tuple | None = None   # mode "interval": the time between two applications (s)
 
 
 @dataclass

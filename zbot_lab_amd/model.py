@@ -157,6 +157,54 @@ class ZbTaskCfg(C.Structure):
     ]
 
 
+class ZbManagerEvents(C.Structure):
+    """include/zbot_manager_events.h ``zb_manager_events``."""
+    _fields_ = [
+        ("push_enabled", C.c_int32), ("push_interval_s", C.c_float * 2),
+        ("push_velocity_range", (C.c_float * 2) * 6), ("cmd_ang_vel_z", C.c_float * 2),
+        ("heading_command", C.c_int32), ("cmd_heading", C.c_float * 2), ("cmd_rel_heading", C.c_float),
+        ("heading_stiffness", C.c_float),
+    ]
+
+
+# rows of the manager's event state (enum zb_manager_event_state_field)
+ME = dict(PUSH_TIME_LEFT=0, HEADING_TARGET=1, IS_HEADING=2)
+ME_STATE_DIM = 3
+PUSH_AXES = ("x", "y", "z", "roll", "pitch", "yaw")  # push_velocity_range rows; absent keys are (0, 0)
+
+
+@dataclass
+class ManagerEvents:
+    """The manager task's interval push and yaw / heading commands (``zb_set_manager_events``): what
+    ``Zbot6BFlatEnvCfg.manager_events()`` compiles ``events.push_robot`` and the ``base_velocity``
+    command's ``ang_vel_z`` / ``heading_command`` into. The default is "events off"."""
+    push_enabled: bool = False
+    push_interval_s: tuple = (0.0, 0.0)
+    push_velocity_range: tuple = ((0.0, 0.0),) * 6
+    cmd_ang_vel_z: tuple = (0.0, 0.0)
+    heading_command: bool = False
+    cmd_heading: tuple = (0.0, 0.0)
+    cmd_rel_heading: float = 1.0
+    heading_stiffness: float = 1.0
+
+    @property
+    def enabled(self) -> bool:
+        return bool(self.push_enabled or self.heading_command or tuple(self.cmd_ang_vel_z) != (0.0, 0.0))
+
+    def pack(self) -> ZbManagerEvents:
+        e = ZbManagerEvents()
+        e.push_enabled = int(self.push_enabled)
+        e.push_interval_s[:] = [float(v) for v in self.push_interval_s]
+        for k, r in enumerate(self.push_velocity_range):
+            e.push_velocity_range[k][:] = [float(v) for v in r]
+        e.cmd_ang_vel_z[:] = [float(v) for v in self.cmd_ang_vel_z]
+        e.heading_command = int(self.heading_command)
+        e.cmd_heading[:] = [float(v) for v in self.cmd_heading]
+        e.cmd_rel_heading = float(self.cmd_rel_heading)
+        e.heading_stiffness = float(self.heading_stiffness)
+        return e
+
+
 # ----------------------------------------------------------------------------- math helpers
 def qmul(a, b):
     aw, ax, ay, az = a

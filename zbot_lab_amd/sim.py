@@ -46,6 +46,7 @@ class ZbotSim:
             nat.check(self.lib.zb_create(C.byref(self._m), C.byref(self._c), self.num_envs, idx, int(seed) & (2**64 - 1),
                                          C.byref(h)), "zb_create")
         self._h = h
+        self.events_configured = False   # set_manager_events has been called (manager task)
         if self.lib.zb_state_dim(h) != self.state_dim:
             raise nat.ZbotError("libzbot state layout does not match zbot_lab_amd.model")
         # persistent outputs (reference: terminated/truncated buffers are mutated in place)
@@ -149,6 +150,36 @@ class ZbotSim:
         out = torch.empty(self.num_envs, self.critic_obs_dim, dtype=torch.float32, device=self.device)
         nat.check(self.lib.zb_observe_critic(self._h, nat.ptr(out), _stream(self.device)), "zb_observe_critic")
         return out
+
+    # ------------------------------------------------------------------ manager events
+    def set_manager_events(self, events: zm.ManagerEvents) -> None:
+        """Manager task: configure the interval push and the yaw / heading commands
+        (zb_set_manager_events; include/zbot_manager_events.h). Draws the push timers and the command's
+        ang z / heading at the current stream position: call it right after construction."""
+        self._events = events.pack()
+        nat.check(self.lib.zb_set_manager_events(self._h, C.byref(self._events), _stream(self.device)),
+                  "zb_set_manager_events")
+        self.events_configured = True
+
+    @property
+    def events_active(self) -> bool:
+        """Whether the next step launches zb_m_events_step_kernel instead of zb_m_step_kernel."""
+        return bool(self.lib.zb_manager_events_active(self._h))
+
+    def get_event_state(self) -> torch.Tensor:
+        """The per-env event state [ME_STATE_DIM, N]: push time left, heading target, is-heading flag."""
+        ev = torch.empty(zm.ME_STATE_DIM, self.num_envs, dtype=torch.float32, device=self.device)
+        nat.check(self.lib.zb_get_manager_event_state(self._h, nat.ptr(ev), _stream(self.device)),
+                  "zb_get_manager_event_state")
+        return ev
+
+    def set_event_state(self, ev: torch.Tensor) -> None:
+        e = ev.to(device=self.device, dtype=torch.float32).contiguous()
+        if e.shape != (zm.ME_STATE_DIM, self.num_envs):
+            raise ValueError(f"event state must be [{zm.ME_STATE_DIM}, {self.num_envs}]")
+        nat.check(self.lib.zb_set_manager_event_state(self._h, nat.ptr(e), _stream(self.device)),
+                  "zb_set_manager_event_state")
+        torch.cuda.current_stream(self.device).synchronize()  # `e` may be a temporary
 
     def set_log_accumulator(self, acc: torch.Tensor | None) -> None:
         """Register a device float[ZB_LOG_LEN + ZB_LOG_COUNTS] accumulator that every later step adds the
