@@ -480,6 +480,10 @@ int zb_pair_manifold_mode(const float* pairs, int n, float margin, int mode, flo
  * the oracle compiles against and which therefore do not change; declared in their own header. */
 #include "zbot_manager_events.h"
 
+/* The manager task's per-env base mass and centre of mass (zb_set_base_inertia and its accessors): the
+ * startup events add_base_mass / base_com, in a side buffer of their own; declared in their own header. */
+#include "zbot_base_inertia.h"
+
 #ifdef __cplusplus
 }
 #endif

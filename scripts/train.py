@@ -72,6 +72,13 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--heading_command", action="store_true", default=False,
                    help="heading_command=True with ranges.heading = (-pi, pi): the yaw command tracks a heading "
                         "target, clipped to --ang_vel_z (default +-1.0 rad/s)")
+    g.add_argument("--add_base_mass", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="restore the base cfg's startup event events.add_base_mass on body 'base': one uniform sample "
+                        "per env, combined with the authored mass by --base_mass_op (kg for add / abs)")
+    g.add_argument("--base_mass_op", choices=("add", "scale", "abs"), default="add", help="with --add_base_mass")
+    g.add_argument("--base_com", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                   help="restore events.base_com on body 'base': COM offset ~ U(-X, X), U(-Y, Y), U(-Z, Z) per env "
+                        "(half-widths, m, link frame)")
     ap.add_argument("--env", action="append", default=[], metavar="PATH=VALUE",
                     help="env cfg override by dotted path, e.g. solver.iterations=8 (simulator ablations)")
     return ap
@@ -97,6 +104,22 @@ def apply_manager_events(env_cfg, args) -> None:
         az = tuple(args.ang_vel_z) if args.ang_vel_z is not None else (-1.0, 1.0)
         cmd.ranges.ang_vel_z = az
         cmd.limit_ranges.ang_vel_z = az
+
+
+def apply_base_inertia(env_cfg, args) -> None:
+    """--add_base_mass / --base_mass_op / --base_com onto the manager env cfg; any other task refuses them."""
+    mass, com = getattr(args, "add_base_mass", None), getattr(args, "base_com", None)
+    if mass is None and com is None:
+        return
+    from zbot_lab_amd.envs.manager_flat import EventTerm, Zbot6BFlatEnvCfg
+    if not isinstance(env_cfg, Zbot6BFlatEnvCfg):
+        raise SystemExit(f"--add_base_mass / --base_com are manager-env options (zbot-6b-walking-m-*), not for {args.task}")
+    if mass is not None:
+        env_cfg.events.add_base_mass = EventTerm("randomize_rigid_body_mass", "startup", {
+            "mass_distribution_params": tuple(mass), "operation": getattr(args, "base_mass_op", "add")})
+    if com is not None:
+        env_cfg.events.base_com = EventTerm("randomize_rigid_body_com", "startup", {
+            "com_range": {k: (-abs(v), abs(v)) for k, v in zip("xyz", com)}})
 
 
 def update_rsl_rl_cfg(agent_cfg, args):
@@ -146,6 +169,7 @@ def main(argv=None) -> dict:
     if args.critic_obs:
         env_cfg.critic_observations = True
     apply_manager_events(env_cfg, args)
+    apply_base_inertia(env_cfg, args)
     zbot_lab_amd.tasks.apply_env_overrides(env_cfg, args.env)
 
     rank, local_rank = 0, 0

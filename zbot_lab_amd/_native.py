@@ -76,7 +76,13 @@ def lib():
     L.zb_manager_event_state_dim.argtypes = [P]
     L.zb_get_manager_event_state.argtypes = [P, P, P]
     L.zb_set_manager_event_state.argtypes = [P, P, P]
-    for name in EXPORTED_CRITIC_OBS + EXPORTED_MANAGER_EVENTS:
+    L.zb_set_base_link.argtypes = [P, C.POINTER(zm.ZbBaseLink)]
+    L.zb_set_base_inertia.argtypes = [P, P, C.c_int, P]
+    L.zb_base_inertia_active.argtypes = [P]
+    L.zb_base_inertia_check.argtypes = [P, P]
+    L.zb_get_base_inertia.argtypes = [P, P, P]
+    L.zb_get_base_link_com.argtypes = [P, P, P]
+    for name in EXPORTED_CRITIC_OBS + EXPORTED_MANAGER_EVENTS + EXPORTED_BASE_INERTIA:
         getattr(L, name).restype = C.c_int
     for name in ("zb_create", "zb_num_envs", "zb_reset", "zb_step", "zb_observe", "zb_kernel_variant", "zb_read_log", "zb_set_log_buffers", "zb_set_log_accumulator", "zb_set_done_buffer",
                  "zb_get_state", "zb_set_state", "zb_get_contact_cache", "zb_set_contact_cache", "zb_physics_substeps",
@@ -98,6 +104,9 @@ EXPORTED_CRITIC_OBS = ["zb_critic_obs_dim", "zb_set_critic_obs_buffer", "zb_obse
 # include/zbot_manager_events.h: the manager task's interval push and yaw / heading commands, likewise
 EXPORTED_MANAGER_EVENTS = ["zb_set_manager_events", "zb_manager_events_active", "zb_manager_event_state_dim",
                            "zb_get_manager_event_state", "zb_set_manager_event_state"]
+# include/zbot_base_inertia.h: the manager task's per-env base mass and COM, likewise
+EXPORTED_BASE_INERTIA = ["zb_set_base_link", "zb_set_base_inertia", "zb_base_inertia_active", "zb_base_inertia_check",
+                         "zb_get_base_inertia", "zb_get_base_link_com"]
 
 
 def check(rc: int, what: str) -> None:

@@ -4,6 +4,9 @@
 // include/zbot_manager_events.h compiled in; two more arguments, the configuration and the event-state
 // side buffer). One text, so the two cannot drift; two kernels, because a shared __device__ body does
 // not reproduce the events-off code (profiles/manager_events/kernel_resources.txt).
+// A third stamp, zb_m_dr_step_kernel (ZB_M_EVENTS 1, ZB_M_BI 1): the events build with the base composite
+// body's mass properties per env (include/zbot_base_inertia.h; one more argument, the side buffer
+// float4[N][4]: the body's three table rows, then the base link's COM in the body frame).
 template <bool kTgs, int kOcc>
 __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg, int N, float* __restrict__ st,
@@ -11,9 +14,10 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     uint8_t* __restrict__ trunc, int64_t* __restrict__ done, float* __restrict__ acc,
     const Counters* __restrict__ cnt, uint64_t seed, ZB_M_EV_PARAMS float* __restrict__ wc) {
   constexpr bool kEvents = ZB_M_EVENTS != 0 && kOcc > 0;  // (value-dependent: the other branch is discarded)
+  constexpr bool kBi = ZB_M_BI != 0 && kOcc > 0;
   const MEv<kEvents> ev ZB_M_EV_INIT;
   MP m = to_mp(mg);
-  __shared__ float4 lds[LDS4];
+  __shared__ float4 lds[LDS4 + (ZB_M_BI ? BI4 : 0)];
   if (kOcc == 1) asm volatile("" ::: "a255");  // (zb_step_kernel: kOcc)
   const int lane = threadIdx.x;
   const int env = xcd_block(blockIdx.x, gridDim.x) * EPW + lane / TL;
@@ -21,6 +25,9 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
   const bool lead = env < N && lane % TL == 0;
   const Q q = make_q(lds, lane, links);
   for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
+  if constexpr (kBi) {  // the env's rows of the base body, read by its lane in every substep's fk_team
+    if (q.s < 3) q.bi()[q.s] = ZB_M_BI_ROWS[(size_t)i * 4 + q.s];
+  }
   Stamps sp;
   sp.begin();
   Phys p;
@@ -89,7 +96,7 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
 #pragma unroll
       for (int j = 0; j < ND; ++j) pv.jqd_prev[j] = p.jqd[j];
     }
-    substep<false, true, kTgs>(m, cfg, p, target, q, true, true, so, nullptr, nullptr, sp);
+    substep<false, true, kTgs, false, false, kBi>(m, cfg, p, target, q, true, true, so, nullptr, nullptr, sp);
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
       const float fn = sqrtf(dot3(so.feet_f[f], so.feet_f[f]));
@@ -119,6 +126,11 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
   // post-step articulation data: root (= base link) pose, link-origin / COM velocity, angular
   // velocity; feet link poses and COM velocities
   float bq[4], bp[3], vb[3], vcom[3], wb[3], feet[2][3], fq[2][4], fvel[2][3];
+  float blc[3] = {0.f, 0.f, 0.f};  // kBi: this env's base-link COM (body frame)
+  if constexpr (kBi) {
+    const float4 c = ZB_M_BI_ROWS[(size_t)i * 4 + 3];
+    blc[0] = c.x; blc[1] = c.y; blc[2] = c.z;
+  }
   {
     wave_sync();
     fk_team_pose(p, q);
@@ -130,7 +142,7 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
 #pragma unroll
     for (int a = 0; a < 3; ++a) bp[a] += p.pos[a];
     link_origin_vel_q(m, q, p, S, B, vb);
-    link_com_vel_q(m, q, p, S, B, vcom);
+    link_com_vel_q<kBi>(m, q, p, S, B, vcom, blc);
     body_ang_vel_q(p, S, link_body(B), wb);
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
@@ -310,7 +322,7 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     if (ev.c.push_enabled) {
       push_t -= step_dt;
       if (push_t < 1e-6f && !reset) {
-        m_push(m, q, ev.c, hs, p);
+        m_push<kBi>(m, q, ev.c, hs, p, blc);
         push_t = m_uniform(hs, M_DRAW_PUSH_T, ev.c.push_interval_s);
       }
     }

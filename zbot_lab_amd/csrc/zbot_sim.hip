@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include <type_traits>
+#include <vector>
 
 #include "zbot.h"
 
@@ -665,6 +666,11 @@ constexpr int LOGR_W = ZB_MAX_REWARD_TERMS + 8;  // = ACC (episode-log entries, 
 constexpr int CARRY0 = ZB_S_P_DELTA, CARRY_W = 64;  // state rows [CARRY0, CARRY0 + CARRY_W)
 constexpr int CARRY_OFF = SENS_OFF + EPW * MAXSUB * 2;
 constexpr int LDS4 = CARRY_OFF + EPW * CARRY_W / 4;
+// per-env rows of the base composite body (include/zbot_base_inertia.h): only the kernels built for them
+// declare these granules, which fill a one-wave workgroup's 20 KB exactly
+constexpr int BI_OFF = LDS4, BI4 = EPW * 3;
+constexpr int BASE_BODY = link_body(6);  // the composite body of the base link (6; 5 in the manager's model)
+static_assert(link_body(5) == BASE_BODY && (LDS4 + BI4) * 16 <= 20 * 1024, "base body; LDS budget");
 constexpr int STG_LEN = 88 + 25 + 3;  // >= max state dim + max obs dim + {reward, term, trunc}
 constexpr int LOGR_OFF = (EPW * STG_LEN + 3) / 4;  // region U, after STG
 static_assert(LOGR_OFF + EPW * LOGR_W / 4 <= U_END, "STG + LOGR fit region U");
@@ -708,6 +714,8 @@ struct Q {
   __device__ __forceinline__ float& stg(int k) const;  // epilogue staging row of this env (staged_store)
   __device__ __forceinline__ float* logr(int ee) const { return reinterpret_cast<float*>(b + LOGR_OFF) + ee * LOGR_W; }
   __device__ __forceinline__ float* carry() const { return reinterpret_cast<float*>(b + CARRY_OFF) + e * CARRY_W; }
+  // this env's rows of the base composite body, behind the carry (kernels with BI4 more granules only)
+  __device__ __forceinline__ float4* bi() const { return b + BI_OFF + e * 3; }
 };
 
 __device__ __forceinline__ Q make_q(float4* lds, int lane, const float4* links) {
@@ -799,7 +807,9 @@ __device__ __forceinline__ void fk_scan_step(float qv[4], float tv[3], int lane_
   for (int a = 0; a < 3; ++a) tv[a] = on ? ts[a] + rt[a] : tv[a];
 }
 
-template <bool kInertia>
+// kBi: the lane of the base composite body reads its three table rows from the env's own rows (q.bi(),
+// include/zbot_base_inertia.h): another LDS address for that one lane, nothing else changes.
+template <bool kInertia, bool kBi = false>
 __device__ __forceinline__ void fk_team(const Phys& s, const Q& q, SI& Ib, float (&Sown)[6]) {
   const int b = q.s;
   if (kInertia) {
@@ -867,6 +877,7 @@ __device__ __forceinline__ void fk_team(const Phys& s, const Q& q, SI& Ib, float
     }
     if (kInertia) {  // spatial inertia of body b about P (world axes)
       const float4* B = q.btab(b);
+      if constexpr (kBi) B = b == BASE_BODY ? q.bi() : B;
       const float4 cm = B[0], i0 = B[1], i1 = B[2];
       float c[3];
       mv3f(R, cm, c);
@@ -2323,7 +2334,8 @@ __device__ __forceinline__ void refresh_contacts(const zb_task_cfg& cfg, MP m, c
 // otherwise cfg.friction everywhere.
 // kRefresh (zb_task_cfg.solver_mode 2 / 3, with kTgs): before every sub-iteration after the first the
 // ground contacts (mode 3: and the self contacts) are re-evaluated at the pose the sub-iterations so far reached (see the sweeps).
-template <bool kDebugForces, bool kLinkFriction, bool kTgs, bool kRefresh = false, bool kRf = false>
+// kBi: the base composite body's mass properties per env (fk_team<true, kBi>).
+template <bool kDebugForces, bool kLinkFriction, bool kTgs, bool kRefresh = false, bool kRf = false, bool kBi = false>
 __device__ __forceinline__ void substep(MP m0, const zb_task_cfg& cfg, Phys& s,
                                         const float target[ND], const Q& q, bool last, bool warm, SensorOut& so,
                                         float (*dbgF)[3], float* dbgTau, Stamps& sp) {
@@ -2349,7 +2361,7 @@ __device__ __forceinline__ void substep(MP m0, const zb_task_cfg& cfg, Phys& s,
   int nc;
   bool over;
   wave_sync();  // the previous substep's LDS readers are done
-  fk_team<true>(s, q, Ib, Sown);
+  fk_team<true, kBi>(s, q, Ib, Sown);
   wave_sync();
   sp.mark(9);
   nc = detect<kRf>(cfg, s.pos[2], q, warm, over, sp);
@@ -2897,8 +2909,10 @@ __device__ __forceinline__ void link_origin_vel_q(MP m, const Q& q, const Phys& 
 }
 
 // world linear velocity of link l's COM: body b's twist at P from the joint rates, then v + w x c
+// kLc: the link's COM (body frame) from lcp instead of the model (the per-env base-link COM)
+template <bool kLc = false>
 __device__ __forceinline__ void link_com_vel_q(MP m, const Q& q, const Phys& s, const float S[ND][6], int l,
-                                               float v[3]) {
+                                               float v[3], const float* lcp = nullptr) {
   const int b = link_body(l);
   float V[6] = {s.av[0], s.av[1], s.av[2], s.lv[0], s.lv[1], s.lv[2]};
 #pragma unroll
@@ -2908,7 +2922,8 @@ __device__ __forceinline__ void link_com_vel_q(MP m, const Q& q, const Phys& s, 
       for (int a = 0; a < 6; ++a) V[a] += S[j][a] * s.jqd[j];
   float R[9], p[3], lc[3], c[3];
   read_frame(q, b, R, p);
-  ldc(lc, m->link_com[l]);
+  if constexpr (kLc) { lc[0] = lcp[0]; lc[1] = lcp[1]; lc[2] = lcp[2]; }
+  else ldc(lc, m->link_com[l]);
   mv3(R, lc, c);
   c[0] += p[0]; c[1] += p[1]; c[2] += p[2];
   float wc[3];
@@ -4577,14 +4592,18 @@ __device__ __forceinline__ void m_heading_cmd(const zb_manager_events& ev, const
 // root (the base link, zb_model.api_root_link) at its COM c, joint rates unchanged: one rigid velocity
 // field dv + dw x (x - c) over the whole robot, i.e. in the chain root's twist (linear part at
 // p.pos) av += dw, lv += dv - dw x (c - p.pos). Reads the published body frames of the current pose.
-__device__ __forceinline__ void m_push(MP m, const Q& q, const zb_manager_events& ev, uint64_t h, Phys& p) {
+// kLc: the root link's COM (body frame) from lcp instead of the model (the per-env base-link COM).
+template <bool kLc = false>
+__device__ __forceinline__ void m_push(MP m, const Q& q, const zb_manager_events& ev, uint64_t h, Phys& p,
+                                       const float* lcp = nullptr) {
   float d[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) d[k] = m_uniform(h, M_DRAW_PUSH + k, ev.push_velocity_range[k]);
   const int l = m->api_root_link;
   float R[9], pb[3], lc[3], c[3], wc[3];
   read_frame(q, link_body(l), R, pb);
-  ldc(lc, m->link_com[l]);
+  if constexpr (kLc) { lc[0] = lcp[0]; lc[1] = lcp[1]; lc[2] = lcp[2]; }
+  else ldc(lc, m->link_com[l]);
   mv3(R, lc, c);
 #pragma unroll
   for (int a = 0; a < 3; ++a) c[a] += pb[a];
@@ -4647,6 +4666,8 @@ static_assert(sizeof(PreM) <= 16 * PRE4, "PreM fits PRE4 granules");
 #define ZB_M_EVENTS 0
 #define ZB_M_EV_PARAMS
 #define ZB_M_EV_INIT {}
+#define ZB_M_BI 0
+#define ZB_M_BI_ROWS static_cast<const float4*>(nullptr)
 #include "zbot_m_step.inc"
 #undef ZB_M_STEP_KERNEL
 #undef ZB_M_EVENTS
@@ -4658,9 +4679,121 @@ static_assert(sizeof(PreM) <= 16 * PRE4, "PreM fits PRE4 granules");
 #define ZB_M_EV_INIT {evc, evst}
 #include "zbot_m_step.inc"
 #undef ZB_M_STEP_KERNEL
+#undef ZB_M_EV_PARAMS
+#undef ZB_M_BI
+#undef ZB_M_BI_ROWS
+// the events build with the per-env base inertia (include/zbot_base_inertia.h)
+#define ZB_M_STEP_KERNEL zb_m_dr_step_kernel
+#define ZB_M_EV_PARAMS zb_manager_events evc, float* __restrict__ evst, const float4* __restrict__ bi,
+#define ZB_M_BI 1
+#define ZB_M_BI_ROWS bi
+#include "zbot_m_step.inc"
+#undef ZB_M_STEP_KERNEL
 #undef ZB_M_EVENTS
 #undef ZB_M_EV_PARAMS
 #undef ZB_M_EV_INIT
+#undef ZB_M_BI
+#undef ZB_M_BI_ROWS
+
+// ------------------------------------------------------------- per-env base mass and COM
+// include/zbot_base_inertia.h. The side buffer is float4[N][4]: the base composite body's three table
+// rows {com, mass}, {Ixx Iyy Izz Ixy}, {Ixz Iyz 0 0} as q.btab holds them, then the base link's COM (body
+// frame). One thread per env sums the body again from the authored base link with the env's mass and
+// COM offset and the body's other links, in fp64, rounded once.
+__device__ __forceinline__ void bi_shift(double m, const double c[3], const double C[3], double I[6]) {
+  const double d[3] = {c[0] - C[0], c[1] - C[1], c[2] - C[2]};
+  const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+  I[0] += m * (dd - d[0] * d[0]); I[1] += m * (dd - d[1] * d[1]); I[2] += m * (dd - d[2] * d[2]);
+  I[3] -= m * d[0] * d[1]; I[4] -= m * d[0] * d[2]; I[5] -= m * d[1] * d[2];
+}
+__global__ void zb_base_inertia_kernel(int N, const float* __restrict__ mass_com, int recompute, zb_base_link L,
+                                       float4* __restrict__ out, int* __restrict__ flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const float* mc = mass_com + (size_t)i * 4;
+  const float4 in = make_float4(mc[0], mc[1], mc[2], mc[3]);
+  // positive and finite, on the bits (the build's finite-math flags fold a float test away)
+  const uint32_t mb = __float_as_uint(in.x);
+  bool ok = mb > 0u && mb < 0x7f800000u;
+  const float off[3] = {in.y, in.z, in.w};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) ok = ok && (__float_as_uint(off[a]) & 0x7f800000u) != 0x7f800000u;
+  if (!ok) {  // keep the env's rows; zb_base_inertia_check reports it
+    *flag = 1;
+    return;
+  }
+  const double m = (double)in.x;
+  const double sc = recompute ? m / L.mass : 1.0;
+  double c0[3], C[3], I[6];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    c0[a] = L.com[a] + (L.rot[3 * a] * (double)off[0] + L.rot[3 * a + 1] * (double)off[1] + L.rot[3 * a + 2] * (double)off[2]);
+  const double M = m + L.rest_mass;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) C[a] = (m * c0[a] + L.rest_mass * L.rest_com[a]) / M;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) I[a] = L.inertia[a] * sc + L.rest_inertia[a];
+  bi_shift(m, c0, C, I);
+  bi_shift(L.rest_mass, L.rest_com, C, I);
+  float4* o = out + (size_t)i * 4;
+  o[0] = make_float4((float)C[0], (float)C[1], (float)C[2], (float)M);
+  o[1] = make_float4((float)I[0], (float)I[1], (float)I[2], (float)I[3]);
+  o[2] = make_float4((float)I[4], (float)I[5], 0.f, 0.f);
+  o[3] = make_float4((float)c0[0], (float)c0[1], (float)c0[2], 0.f);
+}
+
+// the side buffer's floats [r0, r0 + rows) of every env as SoA float[rows][N] (zb_get_base_inertia)
+__global__ void zb_base_inertia_rows_kernel(int N, const float4* __restrict__ bi, int r0, int rows, float* __restrict__ dst) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= N * rows) return;
+  const int r = t / N, i = t % N;
+  dst[(size_t)r * N + i] = reinterpret_cast<const float*>(bi)[(size_t)i * 16 + r0 + r];
+}
+
+// zb_physics_substeps of a handle with the per-env base inertia on: zb_substeps_kernel<true, kTgs> (the
+// manager task's: per-link friction, no refresh) with the env's rows staged for fk_team. A kernel of its
+// own, so that zb_substeps_kernel keeps its name and code.
+template <bool kTgs>
+__global__ __launch_bounds__(WGT, ZB_WAVES_PER_SIMD) void zb_bi_substeps_kernel(
+    const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg, int N, float* __restrict__ st,
+    const float* __restrict__ targets, int nsub, float* __restrict__ net_force, float* __restrict__ tau_out,
+    const float4* __restrict__ bi) {
+  MP m = to_mp(mg);
+  __shared__ float4 lds[LDS4 + BI4];
+  const int lane = threadIdx.x;
+  const int env = xcd_block(blockIdx.x, gridDim.x) * EPW + lane / TL;
+  const int i = env < N ? env : N - 1;
+  const Q q = make_q(lds, lane, links);
+  for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
+  if (q.s < 3) q.bi()[q.s] = bi[(size_t)i * 4 + q.s];
+  if (q.s < NL) {
+    q.fric(q.s) = st[(size_t)(ZB_M_LINK_MU + q.s) * N + i];
+    q.fricd(q.s) = st[(size_t)(ZB_M_LINK_MU_D + q.s) * N + i];
+  }
+  Phys p;
+  load_phys(st, N, i, p);
+  float tg[ND], tau[ND], F[1][3];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) { tg[j] = targets[(size_t)i * ND + j]; tau[j] = 0.f; }
+  SensorOut so;
+  Stamps sp;
+  for (int k = 0; k < nsub; ++k)
+    substep<true, true, kTgs, false, true, true>(m, cfg, p, tg, q, k == nsub - 1, k > 0, so, F, tau, sp);
+  if (net_force && q.s < NL)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) net_force[((size_t)i * NL + q.s) * 3 + a] = F[0][a];
+  if (tau_out)
+#pragma unroll
+    for (int j = 0; j < ND; ++j) tau_out[(size_t)i * ND + j] = tau[j];
+#define SV(f, v) st[(size_t)(f) * N + i] = (v)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { SV(ZB_S_ROOT_POS + a, p.pos[a]); SV(ZB_S_ROOT_LINVEL + a, p.lv[a]); SV(ZB_S_ROOT_ANGVEL + a, p.av[a]); }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) SV(ZB_S_ROOT_QUAT + a, p.quat[a]);
+#pragma unroll
+  for (int j = 0; j < ND; ++j) { SV(ZB_S_JOINT_POS + j, p.jq[j]); SV(ZB_S_JOINT_VEL + j, p.jqd[j]); }
+#undef SV
+}
 
 // command of a reset env redrawn after lin_vel_cmd_levels widened the ranges (zb_finalize_kernel):
 // the post-reset state has zero velocity, so the first metric update reads |command| only
@@ -5083,6 +5216,12 @@ struct zb_sim {
   zb_manager_events ev = {};
   float* d_ev = nullptr;
   bool ev_on = false;
+  // manager task, include/zbot_base_inertia.h: the side buffer (float4[n][4], allocated and filled with the
+  // nominal rows by zb_create), the refused-mass flag, the authored base link, whether the feature is on
+  float4* d_bi = nullptr;
+  int* d_bi_flag = nullptr;
+  zb_base_link base_link = {};
+  bool bi_on = false;
 };
 
 static thread_local char g_err[512] = "";
@@ -5403,6 +5542,23 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
   if (h->task == ZB_TASK_MANAGER_V0) {  // the event state (include/zbot_manager_events.h): zero while events are off
     HIPCHK(hipMalloc(&h->d_ev, sizeof(float) * ZB_ME_STATE_DIM * (size_t)num_envs), "hipMalloc event state");
     HIPCHK(hipMemset(h->d_ev, 0, sizeof(float) * ZB_ME_STATE_DIM * (size_t)num_envs), "hipMemset event state");
+    // the per-env base inertia (include/zbot_base_inertia.h): the nominal rows while the feature is off
+    if (m->api_root_link != m->base_link)
+      return set_err(-1, "zb_create: the manager task's articulation root is its base link", hipSuccess);
+    std::vector<float4> rows((size_t)num_envs * 4);
+    const int bl = m->base_link;
+    const float* I = m->body_inertia[BASE_BODY];
+    for (int i = 0; i < num_envs; ++i) {
+      float4* t = rows.data() + (size_t)i * 4;
+      t[0] = make_float4(m->body_com[BASE_BODY][0], m->body_com[BASE_BODY][1], m->body_com[BASE_BODY][2], m->body_mass[BASE_BODY]);
+      t[1] = make_float4(I[0], I[1], I[2], I[3]);
+      t[2] = make_float4(I[4], I[5], 0.f, 0.f);
+      t[3] = make_float4(m->link_com[bl][0], m->link_com[bl][1], m->link_com[bl][2], 0.f);
+    }
+    HIPCHK(hipMalloc(&h->d_bi, sizeof(float4) * rows.size()), "hipMalloc base inertia");
+    HIPCHK(hipMemcpy(h->d_bi, rows.data(), sizeof(float4) * rows.size(), hipMemcpyHostToDevice), "hipMemcpy base inertia");
+    HIPCHK(hipMalloc(&h->d_bi_flag, sizeof(int)), "hipMalloc base inertia flag");
+    HIPCHK(hipMemset(h->d_bi_flag, 0, sizeof(int)), "hipMemset base inertia flag");
   }
   HIPCHK(hipDeviceSynchronize(), "zb_create sync");
   *out = h;
@@ -5512,6 +5668,8 @@ void zb_destroy(zb_handle h) {
   (void)hipFree(h->d_state);
   (void)hipFree(h->d_wc);
   (void)hipFree(h->d_ev);
+  (void)hipFree(h->d_bi);
+  (void)hipFree(h->d_bi_flag);
   (void)hipFree(h->d_acc);
   (void)hipFree(h->d_cnt);
   (void)hipFree(h->d_log_means);
@@ -5580,7 +5738,9 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
     with_variant<false>(v, [&](auto t, auto o, auto, auto) { go(zb_v4_step_kernel<t.value, o.value>, h->d_cnt, h->seed); });
   else if (h->task == ZB_TASK_MANAGER_V0)
     with_variant<false>(v, [&](auto t, auto o, auto, auto) {
-      if (h->ev_on) go(zb_m_events_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev);
+      // (events off: h->ev holds nothing enabled, so the dr build draws and pushes nothing more)
+      if (h->bi_on) go(zb_m_dr_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev, h->d_bi);
+      else if (h->ev_on) go(zb_m_events_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev);
       else go(zb_m_step_kernel<t.value, o.value>, h->d_cnt, h->seed);
     });
   else
@@ -5706,6 +5866,58 @@ int zb_set_manager_event_state(zb_handle h, const float* src, void* stream) {
   return 0;
 }
 
+int zb_set_base_link(zb_handle h, const zb_base_link* link) {
+  if (!h || !link) return set_err(-1, "zb_set_base_link", hipSuccess);
+  if (h->task != ZB_TASK_MANAGER_V0)
+    return set_err(-1, "zb_set_base_link: the per-env base mass and COM are manager-task events", hipSuccess);
+  if (!(link->mass > 0.0) || !(link->rest_mass >= 0.0))
+    return set_err(-1, "zb_set_base_link: mass > 0 and rest_mass >= 0", hipSuccess);
+  h->base_link = *link;
+  return 0;
+}
+
+int zb_set_base_inertia(zb_handle h, const float* mass_com, int recompute_inertia, void* stream) {
+  if (!h) return set_err(-1, "zb_set_base_inertia", hipSuccess);
+  if (h->task != ZB_TASK_MANAGER_V0)
+    return set_err(-1, "zb_set_base_inertia: the per-env base mass and COM are manager-task events", hipSuccess);
+  if (!mass_com) {
+    h->bi_on = false;
+    return 0;
+  }
+  if (!(h->base_link.mass > 0.0)) return set_err(-1, "zb_set_base_inertia: call zb_set_base_link first", hipSuccess);
+  zb_base_inertia_kernel<<<(h->n + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->n, mass_com, recompute_inertia != 0,
+                                                                            h->base_link, h->d_bi, h->d_bi_flag);
+  const int rc = launch_check("zb_base_inertia_kernel");
+  if (rc) return rc;
+  h->bi_on = true;
+  return 0;
+}
+
+int zb_base_inertia_active(zb_handle h) { return h && h->bi_on ? 1 : 0; }
+
+int zb_base_inertia_check(zb_handle h, void* stream) {
+  if (!h || !h->d_bi_flag) return set_err(-1, "zb_base_inertia_check (a manager-task handle)", hipSuccess);
+  int flag = 0;
+  HIPCHK(hipMemcpyAsync(&flag, h->d_bi_flag, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync flag");
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+  if (!flag) return 0;
+  HIPCHK(hipMemsetAsync(h->d_bi_flag, 0, sizeof(int), (hipStream_t)stream), "hipMemsetAsync flag");
+  return set_err(-1, "zb_set_base_inertia: a base mass that is not positive and finite (or a non-finite COM offset) was "
+                     "refused; those envs keep their previous rows", hipSuccess);
+}
+
+int zb_get_base_inertia(zb_handle h, float* dst, void* stream) {
+  if (!h || !dst || !h->d_bi) return set_err(-1, "zb_get_base_inertia (a manager-task handle)", hipSuccess);
+  zb_base_inertia_rows_kernel<<<(h->n * ZB_BI_ROWS + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->n, h->d_bi, 0, ZB_BI_ROWS, dst);
+  return launch_check("zb_base_inertia_rows_kernel");
+}
+
+int zb_get_base_link_com(zb_handle h, float* dst, void* stream) {
+  if (!h || !dst || !h->d_bi) return set_err(-1, "zb_get_base_link_com (a manager-task handle)", hipSuccess);
+  zb_base_inertia_rows_kernel<<<(h->n * 3 + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->n, h->d_bi, ZB_BI_ROWS, 3, dst);
+  return launch_check("zb_base_inertia_rows_kernel");
+}
+
 int zb_observe_critic(zb_handle h, float* dst, void* stream) {
   if (!h || !dst) return set_err(-1, "zb_observe_critic", hipSuccess);
   return critic_obs(h, dst, (hipStream_t)stream);
@@ -5761,7 +5973,12 @@ int zb_physics_substeps(zb_handle h, const float* targets, int nsub, float* net_
   const bool refresh = h->cfg.solver_mode >= 2;
 #define ZB_SUB(F, T, R) zb_substeps_kernel<F, T, R><<<blocks, WGT, 0, (hipStream_t)stream>>>(h->d_model, h->d_links, \
                                                  h->cfg, h->n, h->d_state, targets, nsub, net_force, applied_torque)
-  if (dr) {
+  if (h->bi_on) {  // (manager task: no refresh; zb_create)
+    if (tgs) zb_bi_substeps_kernel<true><<<blocks, WGT, 0, (hipStream_t)stream>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state,
+                                                                                 targets, nsub, net_force, applied_torque, h->d_bi);
+    else zb_bi_substeps_kernel<false><<<blocks, WGT, 0, (hipStream_t)stream>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state,
+                                                                               targets, nsub, net_force, applied_torque, h->d_bi);
+  } else if (dr) {
     if (refresh) ZB_SUB(true, true, true);
     else if (tgs) ZB_SUB(true, true, false);
     else ZB_SUB(true, false, false);

@@ -162,7 +162,8 @@ class TerminationsCfg:
 
 @dataclass
 class EventCfg:
-    """mgr.py:164-258; rough_env_cfg.py:37-41 removes add_base_mass, base_com, push_robot."""
+    """mgr.py:164-258; rough_env_cfg.py:37-41 removes add_base_mass, base_com, push_robot (a cfg that
+    restores them compiles: Zbot6BFlatEnvCfg.base_inertia() / manager_events())."""
     init_my_data: EventTerm | None = field(default_factory=lambda: EventTerm("init_my_data", "startup"))
     physics_material: EventTerm | None = field(default_factory=lambda: EventTerm(
         "randomize_rigid_body_material", "startup",
@@ -192,6 +193,33 @@ class SceneCfg:
     env_spacing: float = 2.5
     replicate_physics: bool = True
     terrain_type: str = "plane"                  # flat_env_cfg.py:186
+
+
+@dataclass
+class BaseInertiaEvents:
+    """What ``Zbot6BFlatEnvCfg.base_inertia()`` compiles ``events.add_base_mass`` / ``events.base_com``
+    into: the ranges the env's startup draws from. The default is "off"."""
+    mass_enabled: bool = False
+    mass_range: tuple = (0.0, 0.0)
+    mass_operation: str = "add"
+    recompute_inertia: bool = True
+    com_enabled: bool = False
+    com_range: tuple = ((0.0, 0.0),) * 3
+
+    @property
+    def enabled(self) -> bool:
+        return self.mass_enabled or self.com_enabled
+
+
+_BASE_LINK_MASS = None
+
+
+def base_link_mass() -> float:
+    """The authored mass of the manager env's base link (the default the mass event starts from)."""
+    global _BASE_LINK_MASS
+    if _BASE_LINK_MASS is None:
+        _BASE_LINK_MASS = float(zm.pack_base_link(zm.load_v09_model()).mass)
+    return _BASE_LINK_MASS
 
 
 @dataclass
@@ -251,10 +279,7 @@ class Zbot6BFlatEnvCfg:
                 or any(n is not None and n[0] != -n[1] for n in noise):
             raise NotImplementedError("policy observation group: the compiled terms / symmetric noise only")
         ev = self.events
-        for k in ("add_base_mass", "base_com"):
-            if getattr(ev, k) is not None:
-                raise NotImplementedError(f"event {k} is not compiled (the flat cfg removes it): a per-env base "
-                                          "inertia reaches into the articulated-body pass of every step kernel")
+        self.base_inertia()  # add_base_mass, base_com: raises on the forms not compiled
         pr = ev.reset_base.params["pose_range"]
         if any(pr.get(k, (0.0, 0.0)) != (0.0, 0.0) for k in ("z", "pitch")) or \
                 any(tuple(v) != (0.0, 0.0) for v in ev.reset_base.params["velocity_range"].values()):
@@ -323,6 +348,55 @@ class Zbot6BFlatEnvCfg:
             out.heading_stiffness = float(cmd.heading_control_stiffness)
         return out
 
+    def base_inertia(self) -> "BaseInertiaEvents":
+        """Compile the startup events ``events.add_base_mass`` and ``events.base_com`` into the per-env
+        base mass / COM ranges (``zb_set_base_inertia``; beside ``TaskCfg``, which they leave unchanged).
+        The unedited cfg gives "off". Raises ``NotImplementedError`` on a form that is not compiled,
+        saying what is, and ``ValueError`` when the mass range reaches a mass <= 0."""
+        out = BaseInertiaEvents()
+        compiled = ("compiled: events.add_base_mass = EventTerm('randomize_rigid_body_mass', 'startup', "
+                    "{'mass_distribution_params': (lo, hi), 'operation': 'add' | 'scale' | 'abs'[, 'distribution': "
+                    "'uniform'][, 'recompute_inertia': bool]}) and events.base_com = EventTerm("
+                    "'randomize_rigid_body_com', 'startup', {'com_range': {'x': (lo, hi), 'y': ..., 'z': ...}}), "
+                    "both on body 'base' (asset_cfg absent or 'robot:base')")
+
+        def params_of(name, term, func, required, optional):
+            p = term.params if isinstance(term.params, dict) else None
+            if term.func != func or term.mode != "startup" or p is None or not required <= set(p) \
+                    or not set(p) <= required | optional | {"asset_cfg"} or p.get("asset_cfg", "robot:base") != "robot:base":
+                raise NotImplementedError(f"events.{name}: {term.func!r} / {term.mode!r} / "
+                                          f"{sorted(p) if p is not None else term.params!r} is not compiled; {compiled}")
+            return p
+
+        mass = self.events.add_base_mass
+        if mass is not None:
+            p = params_of("add_base_mass", mass, "randomize_rigid_body_mass", {"mass_distribution_params", "operation"},
+                          {"distribution", "recompute_inertia"})
+            if p["operation"] not in ("add", "scale", "abs") or p.get("distribution", "uniform") != "uniform":
+                raise NotImplementedError(f"events.add_base_mass: operation {p['operation']!r} / distribution "
+                                          f"{p.get('distribution')!r} is not compiled; {compiled}")
+            lo, hi = (float(v) for v in p["mass_distribution_params"])
+            if lo > hi:
+                raise NotImplementedError(f"events.add_base_mass: mass_distribution_params need lo <= hi; {compiled}")
+            m0 = base_link_mass()
+            least = float(min(zm.base_mass_op(m0, lo, p["operation"]), zm.base_mass_op(m0, hi, p["operation"])))
+            if not least > 0.0:
+                raise ValueError(f"events.add_base_mass: {p['operation']} {(lo, hi)} on the base link's {m0:.4f} kg "
+                                 f"reaches a mass of {least:.4f} kg; a rigid body needs a positive mass")
+            out.mass_enabled, out.mass_range, out.mass_operation = True, (lo, hi), p["operation"]
+            out.recompute_inertia = bool(p.get("recompute_inertia", True))
+        com = self.events.base_com
+        if com is not None:
+            p = params_of("base_com", com, "randomize_rigid_body_com", {"com_range"}, set())
+            cr = p["com_range"]
+            if not isinstance(cr, dict) or not set(cr) <= {"x", "y", "z"}:
+                raise NotImplementedError(f"events.base_com: com_range {cr!r} is not compiled; {compiled}")
+            rng = tuple(tuple(float(v) for v in cr.get(k, (0.0, 0.0))) for k in ("x", "y", "z"))
+            if any(a > b for a, b in rng):
+                raise NotImplementedError(f"events.base_com: every com_range needs lo <= hi; {compiled}")
+            out.com_enabled, out.com_range = True, rng
+        return out
+
 
 @dataclass
 class Zbot6BFlatEnvCfg_PLAY(Zbot6BFlatEnvCfg):
@@ -333,6 +407,27 @@ class Zbot6BFlatEnvCfg_PLAY(Zbot6BFlatEnvCfg):
         self.scene.env_spacing = 2.5
         self.observations.policy.enable_corruption = False
         self.commands.base_velocity.ranges = self.commands.base_velocity.limit_ranges
+
+
+BASE_INERTIA_SEED_SALT = 0x6261736D  # the startup mass / COM generator: seed ^ this ("basm")
+
+
+def draw_base_inertia(dr: BaseInertiaEvents, num_envs: int, seed: int | None):
+    """(mass [N], com_offset [N, 3]) float32 host tensors of the startup events: four U(0, 1) columns from
+    a generator seeded with ``seed ^ BASE_INERTIA_SEED_SALT``, scaled to the ranges (a disabled event
+    keeps the authored mass / a zero offset but still consumes its columns)."""
+    g = torch.Generator().manual_seed((seed if seed is not None else 0) ^ BASE_INERTIA_SEED_SALT)
+    u = torch.rand(num_envs, 4, generator=g, dtype=torch.float64)
+    m0 = base_link_mass()
+    mass = torch.full((num_envs,), m0, dtype=torch.float64)
+    if dr.mass_enabled:
+        lo, hi = dr.mass_range
+        mass = torch.as_tensor(zm.base_mass_op(m0, (lo + (hi - lo) * u[:, 0]).numpy(), dr.mass_operation))
+    com = torch.zeros(num_envs, 3, dtype=torch.float64)
+    if dr.com_enabled:
+        r = torch.tensor(dr.com_range, dtype=torch.float64)
+        com = r[:, 0] + (r[:, 1] - r[:, 0]) * u[:, 1:]
+    return mass.float(), com.float()
 
 
 def _active(group) -> list:
@@ -410,6 +505,7 @@ class ZbotManagerBasedRLEnv(ZbotDirectEnvV2):
         events = self.cfg.manager_events()
         if events.enabled:  # right after construction, before the first reset: construction semantics
             self.sim.set_manager_events(events)
+        self._startup_base_inertia()
         ev = self.cfg.events.physics_material
         if ev is None:
             return
@@ -421,6 +517,17 @@ class ZbotManagerBasedRLEnv(ZbotDirectEnvV2):
         bucket_ids = torch.randint(0, nb, (self.num_envs, zm.NUM_LINKS), generator=g)
         self.link_materials = self.material_buckets[bucket_ids]
         self.sim.set_link_friction(self.link_materials[..., 0], self.link_materials[..., 1])
+
+    def _startup_base_inertia(self) -> None:
+        """Startup events add_base_mass / base_com: one uniform sample per env of the base link's mass
+        (through the event's operation, from the authored mass) and of its COM offset, drawn on the host
+        from a generator of their own (so the friction draws of the same seed do not move), one call
+        into the simulator. ``base_mass`` [N] and ``base_com_offset`` [N, 3] keep what was drawn."""
+        dr = self.cfg.base_inertia()
+        if not dr.enabled:
+            return
+        self.base_mass, self.base_com_offset = draw_base_inertia(dr, self.num_envs, self.cfg.seed)
+        self.sim.set_base_inertia(self.base_mass, self.base_com_offset, dr.recompute_inertia)
 
     def _update_log(self) -> None:
         """extras["log"] in ManagerBasedRLEnv._reset_idx order: Episode_Reward/<term> (reward

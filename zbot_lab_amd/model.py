@@ -312,6 +312,36 @@ _AXIS_TO_Z = {  # rotation taking the local z axis onto the joint axis
 }
 
 
+def _link_in_body(l: dict, xf: Xf):
+    """An asset link entry's COM and inertia tensor about that COM, in its composite body's frame."""
+    Rpa = qmat(qnorm(l["principal_axes_wxyz"]))
+    I_link = Rpa @ np.diag(l["diag_inertia"]) @ Rpa.T
+    Rl = qmat(xf.q)
+    return xf.apply(l["com"]), Rl @ I_link @ Rl.T
+
+
+def _composites(link_body, link_mass, link_com, link_I, bodies=None):
+    """Mass, COM and inertia about the COM (body frame) of the composite bodies: the parallel-axis sum
+    over each body's links, in link order. ``bodies``: only these (the other rows stay zero)."""
+    body_mass = np.zeros(NUM_BODIES)
+    body_mc = np.zeros((NUM_BODIES, 3))
+    on = [bodies is None or link_body[i] in bodies for i in range(NUM_LINKS)]
+    for i in range(NUM_LINKS):
+        if on[i]:
+            body_mass[link_body[i]] += link_mass[i]
+            body_mc[link_body[i]] += link_mass[i] * link_com[i]
+    with np.errstate(invalid="ignore"):
+        body_com = body_mc / body_mass[:, None]
+    body_inertia = np.zeros((NUM_BODIES, 3, 3))
+    for i in range(NUM_LINKS):
+        if on[i]:
+            b = link_body[i]
+            d = link_com[i] - body_com[b]
+            m = link_mass[i]
+            body_inertia[b] += link_I[i] + m * (np.dot(d, d) * np.eye(3) - np.outer(d, d))
+    return body_mass, body_com, body_inertia
+
+
 def load_model(path: str = ASSET) -> RobotModel:
     """Build the serial-chain model from a decoded asset whose ``links`` are listed in chain order
     (first link = the simulator's root). Joints may point either way along the chain (a USD whose
@@ -349,28 +379,13 @@ def load_model(path: str = ASSET) -> RobotModel:
     assert body == NUM_BODIES - 1 and len(joints) == NUM_DOF
 
     # composite mass properties (authored link values, used verbatim)
-    body_mass = np.zeros(NUM_BODIES)
-    body_mc = np.zeros((NUM_BODIES, 3))
+    link_mass = np.array([links[n]["mass"] for n in names], float)
     link_com = np.zeros((NUM_LINKS, 3))
     link_I = []
     for i, name in enumerate(names):
-        l = links[name]
-        xf = link_xf[i]
-        com_b = xf.apply(l["com"])
-        link_com[i] = com_b
-        Rpa = qmat(qnorm(l["principal_axes_wxyz"]))
-        I_link = Rpa @ np.diag(l["diag_inertia"]) @ Rpa.T
-        Rl = qmat(xf.q)
-        link_I.append(Rl @ I_link @ Rl.T)
-        body_mass[link_body[i]] += l["mass"]
-        body_mc[link_body[i]] += l["mass"] * com_b
-    body_com = body_mc / body_mass[:, None]
-    body_inertia = np.zeros((NUM_BODIES, 3, 3))
-    for i, name in enumerate(names):
-        b = link_body[i]
-        d = link_com[i] - body_com[b]
-        m = links[name]["mass"]
-        body_inertia[b] += link_I[i] + m * (np.dot(d, d) * np.eye(3) - np.outer(d, d))
+        link_com[i], I = _link_in_body(links[name], link_xf[i])
+        link_I.append(I)
+    body_mass, body_com, body_inertia = _composites(link_body, link_mass, link_com, link_I)
 
     circles = np.zeros((NUM_LINKS, 2, 9))
     spheres = np.zeros((NUM_LINKS, 2, 4))
@@ -442,6 +457,104 @@ V09_ASSET = os.path.join(os.path.dirname(__file__), "assets", "zbot6s_v09_model.
 def load_v09_model() -> RobotModel:
     """ZBOT_6S_V2_CFG on zbot_6s_v09.usd (zbot_cfg.py:959-1005): the manager-based env's robot."""
     return load_model(V09_ASSET)
+
+
+def base_mass_op(default: float, sample, operation: str):
+    """Isaac Lab's randomize_rigid_body_mass: the new mass from the default mass and the sample."""
+    sample = np.asarray(sample, dtype=np.float64)
+    if operation == "add":
+        return default + sample
+    if operation == "scale":
+        return default * sample
+    if operation == "abs":
+        return sample
+    raise NotImplementedError(f"mass operation {operation!r}: 'add', 'scale' and 'abs' are compiled")
+
+
+def _base_links(rm: RobotModel):
+    """(mass, COM, inertia about the COM; body frame, float64) of every link of the composite body that
+    holds ``rm.base_link``, as authored; the base link's index among them; the link indices."""
+    b = rm.link_body[rm.base_link]
+    idx = [i for i in range(NUM_LINKS) if rm.link_body[i] == b]
+    by_name = {l["name"]: l for l in rm.raw["links"]}
+    props = []
+    for i in idx:
+        l = by_name[rm.link_names[i]]
+        com, I = _link_in_body(l, rm.link_xf[i])
+        props.append((float(l["mass"]), com, I))
+    return props, idx.index(rm.base_link), idx
+
+
+def with_base_inertia(rm: RobotModel, mass: float, com_offset, recompute_inertia: bool = True) -> RobotModel:
+    """A copy of ``rm`` whose base link (``rm.base_link``) has mass ``mass`` and its COM moved by
+    ``com_offset`` (link frame), Isaac Lab's randomize_rigid_body_mass / randomize_rigid_body_com:
+    with ``recompute_inertia`` the link's own tensor about its COM scales by mass / default mass, a COM
+    offset leaves it unchanged (PhysX keeps the inertia about the COM). The composite body holding the
+    link is summed again as ``load_model`` sums it; only ``body_mass``, ``body_com``, ``body_inertia``
+    of that body and ``link_com[base_link]`` differ from ``rm``."""
+    import dataclasses
+    mass = float(mass)
+    if not (mass > 0.0 and math.isfinite(mass)):
+        raise ValueError(f"base link mass {mass!r} kg: a rigid body needs a positive finite mass")
+    props, k, idx = _base_links(rm)
+    m0, com0, I0 = props[k]
+    link_mass = np.zeros(NUM_LINKS)
+    link_com = rm.link_com.copy()
+    link_I = [np.zeros((3, 3))] * NUM_LINKS
+    for (m, c, I), i in zip(props, idx):
+        link_mass[i], link_com[i], link_I[i] = m, c, I
+    base = rm.base_link
+    link_mass[base] = mass
+    link_com[base] = com0 + qrot(rm.link_xf[base].q, np.asarray(com_offset, dtype=np.float64))
+    if recompute_inertia:
+        link_I[base] = I0 * (mass / m0)
+    b = rm.link_body[base]
+    bm, bc, bi = _composites(rm.link_body, link_mass, link_com, link_I, bodies=(b,))
+    body_mass, body_com, body_inertia = rm.body_mass.copy(), rm.body_com.copy(), rm.body_inertia.copy()
+    body_mass[b], body_com[b], body_inertia[b] = bm[b], bc[b], bi[b]
+    new_link_com = rm.link_com.copy()
+    new_link_com[base] = link_com[base]
+    return dataclasses.replace(rm, body_mass=body_mass, body_com=body_com, body_inertia=body_inertia,
+                               link_com=new_link_com)
+
+
+class ZbBaseLink(C.Structure):
+    """include/zbot_base_inertia.h ``zb_base_link``."""
+    _fields_ = [
+        ("mass", C.c_double), ("com", C.c_double * 3), ("rot", C.c_double * 9), ("inertia", C.c_double * 6),
+        ("rest_mass", C.c_double), ("rest_com", C.c_double * 3), ("rest_inertia", C.c_double * 6),
+    ]
+
+
+def _sym6(I):
+    return [I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]]
+
+
+def pack_base_link(rm: RobotModel) -> ZbBaseLink:
+    """The authored base link and the rest of its composite body (``zb_set_base_link``), float64."""
+    props, k, idx = _base_links(rm)
+    m0, com0, I0 = props[k]
+    s = ZbBaseLink()
+    s.mass = m0
+    s.com[:] = list(com0)
+    s.rot[:] = list(qmat(rm.link_xf[rm.base_link].q).reshape(-1))
+    s.inertia[:] = _sym6(I0)
+    # the other links of the body as one rigid part about its own COM
+    b = rm.link_body[rm.base_link]
+    link_mass = np.zeros(NUM_LINKS)
+    link_com = np.zeros((NUM_LINKS, 3))
+    link_I = [np.zeros((3, 3))] * NUM_LINKS
+    rest = [i for i in idx if i != rm.base_link]
+    for (m, c, I), i in zip(props, idx):
+        if i != rm.base_link:
+            link_mass[i], link_com[i], link_I[i] = m, c, I
+    if rest:
+        lb = [b if i in rest else -1 for i in range(NUM_LINKS)]
+        bm, bc, bi = _composites(lb, link_mass, link_com, link_I, bodies=(b,))
+        s.rest_mass = bm[b]
+        s.rest_com[:] = list(bc[b])
+        s.rest_inertia[:] = _sym6(bi[b])
+    return s
 
 
 def standup_model(rm: RobotModel | None = None) -> RobotModel:

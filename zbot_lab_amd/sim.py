@@ -181,6 +181,51 @@ class ZbotSim:
                   "zb_set_manager_event_state")
         torch.cuda.current_stream(self.device).synchronize()  # `e` may be a temporary
 
+    # ------------------------------------------------------------------ per-env base mass and COM
+    def set_base_inertia(self, mass: torch.Tensor | None, com_offset: torch.Tensor | None = None,
+                         recompute_inertia: bool = True) -> None:
+        """Manager task: the base link's mass [N] (kg) and COM offset [N, 3] (m, link frame) per env
+        (zb_set_base_inertia; include/zbot_base_inertia.h), Isaac Lab's randomize_rigid_body_mass /
+        randomize_rigid_body_com. ``mass=None`` switches the feature off again. Never synchronises: a mass
+        that is not positive and finite is refused on the device and reported by check_base_inertia()."""
+        if mass is None:
+            nat.check(self.lib.zb_set_base_inertia(self._h, None, 0, _stream(self.device)), "zb_set_base_inertia")
+            return
+        if self.task != zm.TASK_MANAGER_V0:
+            raise nat.ZbotError("set_base_inertia: the per-env base mass and COM are manager-task events")
+        m = mass.to(device=self.device, dtype=torch.float32).reshape(-1)
+        c = (torch.zeros(self.num_envs, 3, device=self.device) if com_offset is None
+             else com_offset.to(device=self.device, dtype=torch.float32))
+        if m.shape != (self.num_envs,) or c.shape != (self.num_envs, 3):
+            raise ValueError(f"mass must be [{self.num_envs}] and com_offset [{self.num_envs}, 3]")
+        if getattr(self, "_base_link", None) is None:
+            self._base_link = zm.pack_base_link(self.robot)
+            nat.check(self.lib.zb_set_base_link(self._h, C.byref(self._base_link)), "zb_set_base_link")
+        self._mass_com = torch.cat([m[:, None], c], dim=1).contiguous()  # kept alive: the launch reads it in stream order
+        nat.check(self.lib.zb_set_base_inertia(self._h, nat.ptr(self._mass_com), int(bool(recompute_inertia)),
+                                               _stream(self.device)), "zb_set_base_inertia")
+
+    @property
+    def base_inertia_active(self) -> bool:
+        """Whether the next step launches zb_m_dr_step_kernel (per-env base mass properties)."""
+        return bool(self.lib.zb_base_inertia_active(self._h))
+
+    def check_base_inertia(self) -> None:
+        """Raise if a set_base_inertia so far was given a mass the device refused (synchronises)."""
+        nat.check(self.lib.zb_base_inertia_check(self._h, _stream(self.device)), "zb_base_inertia_check")
+
+    def get_base_inertia(self) -> torch.Tensor:
+        """The composed rows of the base composite body [12, N]: com xyz, mass, Ixx Iyy Izz Ixy, Ixz Iyz 0 0."""
+        out = torch.empty(12, self.num_envs, dtype=torch.float32, device=self.device)
+        nat.check(self.lib.zb_get_base_inertia(self._h, nat.ptr(out), _stream(self.device)), "zb_get_base_inertia")
+        return out
+
+    def get_base_link_com(self) -> torch.Tensor:
+        """The per-env base-link COM in the body frame [3, N]."""
+        out = torch.empty(3, self.num_envs, dtype=torch.float32, device=self.device)
+        nat.check(self.lib.zb_get_base_link_com(self._h, nat.ptr(out), _stream(self.device)), "zb_get_base_link_com")
+        return out
+
     def set_log_accumulator(self, acc: torch.Tensor | None) -> None:
         """Register a device float[ZB_LOG_LEN + ZB_LOG_COUNTS] accumulator that every later step adds the
         log's current values to inside its finalize launch (zb_set_log_accumulator; the PPO runner's
