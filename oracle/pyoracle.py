@@ -36,6 +36,7 @@ def _load(double: bool = False):
     lib.zbo_create.argtypes = [C.POINTER(zm.ZbModel), C.POINTER(zm.ZbTaskCfg), C.c_int, C.c_uint64]
     lib.zbo_destroy.argtypes = [P]
     lib.zbo_set_threads.argtypes = [C.c_int]
+    lib.zbo_set_model_f64.argtypes = [P, np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")]
     lib.zbo_reset.argtypes = [P, C.c_void_p, C.c_int]
     lib.zbo_step.argtypes = [P, _f, _f, _f, _u8, _u8]
     lib.zbo_observe.argtypes = [P, _f]
@@ -94,6 +95,22 @@ def lib(double: bool = False):
 
 def f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def model_f64(rm: zm.RobotModel) -> np.ndarray:
+    """The rows of ``zb_model`` that enter the dynamics, in float64 (``zbo_set_model_f64``'s layout)."""
+    I = rm.body_inertia
+    sym = np.stack([I[:, 0, 0], I[:, 1, 1], I[:, 2, 2], I[:, 0, 1], I[:, 0, 2], I[:, 1, 2]], axis=1)
+    rows = [rm.body_mass, rm.body_com, sym]
+    for xf, part in (("parent_xf", "p"), ("parent_xf", "q"), ("child_xf", "p"), ("child_xf", "q")):
+        rows.append(np.array([getattr(j[xf], part) for j in rm.joints], np.float64))
+    return np.ascontiguousarray(np.concatenate([np.asarray(r, np.float64).reshape(-1) for r in rows]))
+
+
+def set_model_f64(lib_, handle, rm: zm.RobotModel) -> None:
+    """Replace the float32 mass properties and joint frames of an oracle handle by ``rm``'s float64 ones
+    (meant for the f64 build: its dynamics then carry no float32 rounding of the model)."""
+    lib_.zbo_set_model_f64(handle, model_f64(rm))
 
 
 class OracleSim:

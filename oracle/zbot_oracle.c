@@ -2954,6 +2954,23 @@ void zbo_destroy(zbo_sim* s) {
   free(s);
 }
 
+/* The mass properties and joint frames of the dynamics in double, replacing what load_mdl took from
+ * zb_model's float rows: the f64 build then carries no float32 rounding of the model (2^-24 relative on
+ * every row moves a saturated joint's substep by up to 1e-5, tests/test_oracle_dynamics.py); the f32
+ * build rounds them as zb_model does. Layout: body_mass[7], body_com[7][3], body_inertia[7][6],
+ * joint_parent_pos[6][3], joint_parent_rot[6][4], joint_child_pos[6][3], joint_child_rot[6][4]. */
+int zbo_set_model_f64(zbo_sim* s, const double* v) {
+  mdl_t* m = &s->m;
+  for (int b = 0; b < NB; ++b) m->body_mass[b] = (real)*v++;
+  for (int b = 0; b < NB; ++b) for (int a = 0; a < 3; ++a) m->body_com[b][a] = (real)*v++;
+  for (int b = 0; b < NB; ++b) for (int a = 0; a < 6; ++a) m->body_I[b][a] = (real)*v++;
+  for (int j = 0; j < ND; ++j) for (int a = 0; a < 3; ++a) m->jp_pos[j][a] = (real)*v++;
+  for (int j = 0; j < ND; ++j) for (int a = 0; a < 4; ++a) m->jp_rot[j][a] = (real)*v++;
+  for (int j = 0; j < ND; ++j) for (int a = 0; a < 3; ++a) m->jc_pos[j][a] = (real)*v++;
+  for (int j = 0; j < ND; ++j) for (int a = 0; a < 4; ++a) m->jc_rot[j][a] = (real)*v++;
+  return 0;
+}
+
 int zbo_set_threads(int n) {
 #ifdef _OPENMP
   if (n > 0) omp_set_num_threads(n);
