@@ -484,6 +484,11 @@ int zb_pair_manifold_mode(const float* pairs, int n, float margin, int mode, flo
  * startup events add_base_mass / base_com, in a side buffer of their own; declared in their own header. */
 #include "zbot_base_inertia.h"
 
+/* The manager task's five more reward terms (gait, feet_clearance, feet_air_time, base_vel_forward,
+ * feet_force_pattern: zb_set_manager_terms and the term-state accessors) and zb_kernel_variant_name;
+ * configuration and per-env state in a side buffer of their own; declared in their own header. */
+#include "zbot_manager_terms.h"
+
 #ifdef __cplusplus
 }
 #endif

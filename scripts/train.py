@@ -79,6 +79,11 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--base_com", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                    help="restore events.base_com on body 'base': COM offset ~ U(-X, X), U(-Y, Y), U(-Z, Z) per env "
                         "(half-widths, m, link frame)")
+    g.add_argument("--reward", action="append", default=[], metavar="NAME=WEIGHT",
+                   help="set rewards.NAME.weight (repeatable); a term the flat cfg switches off (gait, feet_clearance, "
+                        "feet_air_time, base_vel_forward, feet_force_pattern) is restored with the base cfg's params")
+    g.add_argument("--no_reward", action="append", default=[], metavar="NAME",
+                   help="rewards.NAME = None (repeatable): the term leaves the reward and the Episode_Reward log")
     ap.add_argument("--env", action="append", default=[], metavar="PATH=VALUE",
                     help="env cfg override by dotted path, e.g. solver.iterations=8 (simulator ablations)")
     return ap
@@ -104,6 +109,38 @@ def apply_manager_events(env_cfg, args) -> None:
         az = tuple(args.ang_vel_z) if args.ang_vel_z is not None else (-1.0, 1.0)
         cmd.ranges.ang_vel_z = az
         cmd.limit_ranges.ang_vel_z = az
+
+
+def apply_manager_rewards(env_cfg, args) -> None:
+    """--reward NAME=WEIGHT / --no_reward NAME onto the manager env cfg's rewards; any other task refuses them."""
+    sets, drops = getattr(args, "reward", []), getattr(args, "no_reward", [])
+    if not sets and not drops:
+        return
+    from dataclasses import fields
+    from zbot_lab_amd.envs.manager_flat import RewardsCfg, Zbot6BFlatEnvCfg, base_reward_term
+    if not isinstance(env_cfg, Zbot6BFlatEnvCfg):
+        raise SystemExit(f"--reward / --no_reward are manager-env options (zbot-6b-walking-m-*), not for {args.task}")
+    names = [f.name for f in fields(RewardsCfg)]
+    for item in sets:
+        name, sep, val = item.partition("=")
+        try:
+            weight = float(val)
+        except ValueError:
+            weight = None
+        if not sep or name not in names or weight is None:
+            raise SystemExit(f"--reward {item!r}: expected NAME=WEIGHT with NAME one of {names}")
+        term = getattr(env_cfg.rewards, name)
+        if term is None:
+            try:
+                term = base_reward_term(name)
+            except KeyError:
+                raise SystemExit(f"--reward {name}: the term is not compiled (task_cfg() says what is)")
+            setattr(env_cfg.rewards, name, term)
+        term.weight = weight
+    for name in drops:
+        if name not in names:
+            raise SystemExit(f"--no_reward {name!r}: expected one of {names}")
+        setattr(env_cfg.rewards, name, None)
 
 
 def apply_base_inertia(env_cfg, args) -> None:
@@ -170,6 +207,7 @@ def main(argv=None) -> dict:
         env_cfg.critic_observations = True
     apply_manager_events(env_cfg, args)
     apply_base_inertia(env_cfg, args)
+    apply_manager_rewards(env_cfg, args)
     zbot_lab_amd.tasks.apply_env_overrides(env_cfg, args.env)
 
     rank, local_rank = 0, 0

@@ -82,8 +82,14 @@ def lib():
     L.zb_base_inertia_check.argtypes = [P, P]
     L.zb_get_base_inertia.argtypes = [P, P, P]
     L.zb_get_base_link_com.argtypes = [P, P, P]
-    for name in EXPORTED_CRITIC_OBS + EXPORTED_MANAGER_EVENTS + EXPORTED_BASE_INERTIA:
+    L.zb_set_manager_terms.argtypes = [P, C.POINTER(zm.ZbManagerTerms), P]
+    L.zb_manager_terms_active.argtypes = [P]
+    L.zb_kernel_variant_name.argtypes = [P]
+    L.zb_get_manager_terms_state.argtypes = [P, P, P]
+    L.zb_set_manager_terms_state.argtypes = [P, P, P]
+    for name in EXPORTED_CRITIC_OBS + EXPORTED_MANAGER_EVENTS + EXPORTED_BASE_INERTIA + EXPORTED_MANAGER_TERMS:
         getattr(L, name).restype = C.c_int
+    L.zb_kernel_variant_name.restype = C.c_char_p
     for name in ("zb_create", "zb_num_envs", "zb_reset", "zb_step", "zb_observe", "zb_kernel_variant", "zb_read_log", "zb_set_log_buffers", "zb_set_log_accumulator", "zb_set_done_buffer",
                  "zb_get_state", "zb_set_state", "zb_get_contact_cache", "zb_set_contact_cache", "zb_physics_substeps",
                  "zb_profile_begin", "zb_profile_end", "zb_profile_stride",
@@ -107,6 +113,9 @@ EXPORTED_MANAGER_EVENTS = ["zb_set_manager_events", "zb_manager_events_active", 
 # include/zbot_base_inertia.h: the manager task's per-env base mass and COM, likewise
 EXPORTED_BASE_INERTIA = ["zb_set_base_link", "zb_set_base_inertia", "zb_base_inertia_active", "zb_base_inertia_check",
                          "zb_get_base_inertia", "zb_get_base_link_com"]
+# include/zbot_manager_terms.h: the manager task's five more reward terms, likewise
+EXPORTED_MANAGER_TERMS = ["zb_set_manager_terms", "zb_manager_terms_active", "zb_kernel_variant_name",
+                          "zb_get_manager_terms_state", "zb_set_manager_terms_state"]
 
 
 def check(rc: int, what: str) -> None:

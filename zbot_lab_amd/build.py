@@ -30,6 +30,7 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False, defi
     out = os.path.join(HERE, out) if out else (STAMPS_OUT if stamps else OUT)
     deps = [SRC, os.path.join(HERE, "csrc", "zbot_m_step.inc"), os.path.join(ROOT, "include", "zbot.h"), os.path.join(ROOT, "include", "zbot_critic_obs.h"),
             os.path.join(ROOT, "include", "zbot_manager_events.h"), os.path.join(ROOT, "include", "zbot_base_inertia.h"),
+            os.path.join(ROOT, "include", "zbot_manager_terms.h"),
             os.path.abspath(__file__)]
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
         return out

@@ -7,6 +7,16 @@
 // A third stamp, zb_m_dr_step_kernel (ZB_M_EVENTS 1, ZB_M_BI 1): the events build with the base composite
 // body's mass properties per env (include/zbot_base_inertia.h; one more argument, the side buffer
 // float4[N][4]: the body's three table rows, then the base link's COM in the body frame).
+// A fourth stamp, zb_m_terms_step_kernel (ZB_M_EVENTS 1, ZB_M_BI 1, ZB_M_TERMS 1): the dr build with the five
+// reward terms of include/zbot_manager_terms.h (two more arguments, both pointers: the configuration's
+// device copy, read in the reward epilogue only, and the term-state side buffer float[ZB_MT_STATE_DIM][N],
+// whose rows ride in the LDS carry behind the event state). The feet's contact timers ride in the air
+// timers' registers through the substep loop (a foot is in one mode at a time: > 0 air time, < 0 minus the
+// contact time); everything else is in the reward epilogue. What the build costs in registers and
+// scratch: profiles/manager_terms/kernel_resources.txt, held by tests/test_manager_terms_resources.py
+// (40 / 56 B at two waves per SIMD against the dr build's 40 / 52 B, none at one; the TGS two-wave build
+// parks a third per-lane 64-bit detection mask in scratch and reloads it inside a detection loop, one
+// in-loop reload more than the dr build; DESIGN.md §9).
 template <bool kTgs, int kOcc>
 __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg, int N, float* __restrict__ st,
@@ -15,7 +25,9 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     const Counters* __restrict__ cnt, uint64_t seed, ZB_M_EV_PARAMS float* __restrict__ wc) {
   constexpr bool kEvents = ZB_M_EVENTS != 0 && kOcc > 0;  // (value-dependent: the other branch is discarded)
   constexpr bool kBi = ZB_M_BI != 0 && kOcc > 0;
+  constexpr bool kTerms = ZB_M_TERMS != 0 && kOcc > 0;
   const MEv<kEvents> ev ZB_M_EV_INIT;
+  const MTerms<kTerms> tm ZB_M_TERMS_INIT;
   MP m = to_mp(mg);
   __shared__ float4 lds[LDS4 + (ZB_M_BI ? BI4 : 0)];
   if (kOcc == 1) asm volatile("" ::: "a255");  // (zb_step_kernel: kOcc)
@@ -40,6 +52,7 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
   const float* cst;  // the friction rows load into FRIC; the event state rides behind the MDP rows
   if constexpr (kEvents) cst = carry_prefetch<ZB_M_LINK_MU, ZB_ME_STATE_DIM>(q, st, N, i, ev.st);
   else cst = carry_prefetch<ZB_M_LINK_MU>(q, st, N, i);
+  if constexpr (kTerms) m_terms_prefetch(q, N, i, tm.st);
   if (q.s < NL) {
     q.fric(q.s) = ST(ZB_M_LINK_MU + q.s);
     q.fricd(q.s) = ST(ZB_M_LINK_MU_D + q.s);
@@ -78,6 +91,14 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
   float fz_h[3][2], fn_h[3][2];
   float air_cur[2] = {ST(ZB_M_FEET_AIR_CUR), ST(ZB_M_FEET_AIR_CUR + 1)};
   float air_last[2] = {ST(ZB_M_FEET_AIR_LAST), ST(ZB_M_FEET_AIR_LAST + 1)};
+  if constexpr (kTerms) {
+    wave_sync();  // (the carry rows of m_terms_prefetch)
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const float ct = CST(M_CST_TERMS + ZB_MT_CONTACT_CUR + f);
+      air_cur[f] = ct > 0.f ? -ct : air_cur[f];
+    }
+  }
   const bool hist_in = cfg.decimation < 3;  // >= 3 substeps overwrite every slot: no read
 #pragma unroll
   for (int h = 0; h < 3; ++h)
@@ -104,13 +125,26 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
       fn_h[2][f] = fn_h[1][f]; fn_h[1][f] = fn_h[0][f]; fn_h[0][f] = fn;
       const bool c = fn > cfg.contact_force_threshold;
       air_last[f] = (air_cur[f] > 0.f && c) ? air_cur[f] + cfg.sim_dt : air_last[f];
-      air_cur[f] = c ? 0.f : air_cur[f] + cfg.sim_dt;
+      if constexpr (kTerms) {  // current_contact_time = c ? t + sim_dt : 0 beside current_air_time, signed
+        const float same = (c ? air_cur[f] < 0.f : air_cur[f] > 0.f) ? air_cur[f] : 0.f;
+        air_cur[f] = c ? same - cfg.sim_dt : same + cfg.sim_dt;
+      } else {
+        air_cur[f] = c ? 0.f : air_cur[f] + cfg.sim_dt;
+      }
     }
     sp.mark(7);
   }
   PreM pr;
   const float wc_row = after_substeps(m, q, st, pr);
 
+  float con_cur[2] = {0.f, 0.f};  // kTerms: ContactSensor current_contact_time of the feet
+  if constexpr (kTerms) {
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      con_cur[f] = fmaxf(-air_cur[f], 0.f);
+      air_cur[f] = fmaxf(air_cur[f], 0.f);
+    }
+  }
   const float ep_len = CST(ZB_M_EP_LEN) + 1.f;
   float cmd[3] = {CST(ZB_M_COMMANDS), CST(ZB_M_COMMANDS + 1), CST(ZB_M_COMMANDS + 2)};
   float tleft = CST(ZB_M_CMD_TIME_LEFT), standing = CST(ZB_M_CMD_STANDING);
@@ -127,6 +161,7 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
   // velocity; feet link poses and COM velocities
   float bq[4], bp[3], vb[3], vcom[3], wb[3], feet[2][3], fq[2][4], fvel[2][3];
   float blc[3] = {0.f, 0.f, 0.f};  // kBi: this env's base-link COM (body frame)
+  float fcz[2] = {0.f, 0.f};       // kTerms: world height of each foot's clearance point
   if constexpr (kBi) {
     const float4 c = ZB_M_BI_ROWS[(size_t)i * 4 + 3];
     blc[0] = c.x; blc[1] = c.y; blc[2] = c.z;
@@ -151,6 +186,11 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
 #pragma unroll
       for (int a = 0; a < 3; ++a) feet[f][a] += p.pos[a];
       link_com_vel_q(m, q, p, S, l, fvel[f]);
+      if constexpr (kTerms) {
+        const float4 rz = q.frame(link_body(l), 2);  // the body pose's {R row 2, p.z} (read_frame)
+        fcz[f] = p.pos[2] + rz.w + (rz.x * tm.c->clearance_point[f][0] + rz.y * tm.c->clearance_point[f][1] +
+                                    rz.z * tm.c->clearance_point[f][2]);
+      }
     }
   }
   // TerminationManager (flat: time_out, base_height < 0.2, feet_close < 0.12)
@@ -163,6 +203,8 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
 
   // RewardManager.compute: term * weight * step_dt in cfg order (mgr.py:262-357, flat overrides)
   float r[ZB_M_NUM_REWARD_TERMS];
+  float xr[ZB_MT_NUM_TERMS], fsum = 0.f;  // kTerms: the five terms, env.feet_force_sum
+  if constexpr (kTerms) fsum = CST(M_CST_TERMS + ZB_MT_FEET_FORCE_SUM);
   {
     float Rb[9];
     qmat(bq, Rb);
@@ -221,6 +263,43 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     r[ZB_M_R_FOOT_FORWARD] = sfw;
     r[ZB_M_R_FEET_SLIDE] = sl;
     r[ZB_M_R_AIR_TIME_BALANCE] = fabsf(air_last[0] - air_last[1]);
+    if constexpr (kTerms) {
+      const zb_manager_terms& tc = *tm.c;
+      const bool in_c0 = con_cur[0] > 0.f, in_c1 = con_cur[1] > 0.f;
+      {  // feet_gait (rewards.py:155-183): fp32 phase arithmetic in the reference's order
+        const float ph = fmod_pos(ep_len * step_dt, tc.gait_period) / tc.gait_period;
+        float n = 0.f;
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          float lp = ph + tc.gait_offset[f];
+          lp -= floorf(lp);  // (% 1, exact)
+          n += ((lp < tc.gait_threshold) == (f == 0 ? in_c0 : in_c1)) ? 1.f : 0.f;
+        }
+        xr[ZB_MT_GAIT] = sqrtf(dot3(cmd, cmd)) > 0.05f ? n : 0.f;
+      }
+      {  // foot_clearance_reward (rewards.py:144-153)
+        float e = 0.f;
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          const float dz = fcz[f] - tc.clearance_target_height;
+          e += dz * dz * tanh_r(tc.clearance_tanh_mult * sqrtf(fvel[f][0] * fvel[f][0] + fvel[f][1] * fvel[f][1]));
+        }
+        xr[ZB_MT_FEET_CLEARANCE] = __expf(-e / tc.clearance_std);
+      }
+      {  // feet_air_time_positive_biped (rewards.py:207-226)
+        const float t0 = in_c0 ? con_cur[0] : air_cur[0], t1 = in_c1 ? con_cur[1] : air_cur[1];
+        const float t = in_c0 != in_c1 ? fminf(fminf(t0, t1), tc.air_time_threshold) : 0.f;
+        xr[ZB_MT_FEET_AIR_TIME] = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]) > 0.1f ? t : 0.f;
+      }
+      xr[ZB_MT_BASE_VEL_FORWARD] = tc.which_forward * (vb[0] * fwd[0] + vb[1] * fwd[1]);  // (rewards.py:266-275)
+      {  // feet_force_pattern (rewards.py:277-287): the sign before the integrator's update, sign(0) = 0
+        const float f0 = (fz_h[0][0] + fz_h[1][0] + fz_h[2][0]) / 3.f, f1 = (fz_h[0][1] + fz_h[1][1] + fz_h[2][1]) / 3.f;
+        const float sg = fsum > 0.f ? 1.f : fsum < 0.f ? -1.f : 0.f;
+        const float nsum = fsum + 0.001f * (f0 - f1);
+        fsum = (tc.active >> ZB_MT_FEET_FORCE_PATTERN) & 1u ? nsum : fsum;
+        xr[ZB_MT_FEET_FORCE_PATTERN] = 0.5f * (f1 - f0) * sg - 0.1f * fabsf(fsum);
+      }
+    }
   }
   float reward = 0.f, sums[ZB_M_NUM_REWARD_TERMS];
 #pragma unroll
@@ -228,6 +307,28 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     const float v = r[t] * cfg.stage_scales[0][t] * step_dt;
     reward += v;
     sums[t] = CST(ZB_M_EP_SUMS + t) + v;
+  }
+  if constexpr (kTerms) {  // the reward again as the sixteen fields' sum in cfg order
+    float xv[ZB_MT_NUM_TERMS];
+#pragma unroll
+    for (int t = 0; t < ZB_MT_NUM_TERMS; ++t) {
+      const float s0 = CST(M_CST_TERMS + ZB_MT_EP_SUMS + t);
+      xv[t] = (tm.c->active >> t) & 1u ? xr[t] * tm.c->weight[t] * step_dt : 0.f;
+      // the term state leaves for its staging entries at once (region U holds nothing else in the
+      // epilogue), so none of it is live through the resets, the command update and the observation
+      if (writer) OUT(M_STG_TERMS + ZB_MT_EP_SUMS + t) = blowup ? s0 : s0 + xv[t];
+    }
+    if (writer) {
+      OUT(M_STG_TERMS + ZB_MT_CONTACT_CUR) = con_cur[0];
+      OUT(M_STG_TERMS + ZB_MT_CONTACT_CUR + 1) = con_cur[1];
+      OUT(M_STG_TERMS + ZB_MT_FEET_FORCE_SUM) = fsum;
+    }
+    reward = 0.f;
+#pragma unroll
+    for (int t = 0; t < ZB_M_NUM_REWARD_TERMS + ZB_MT_NUM_TERMS; ++t) {
+      const int s = M_CFG_ORDER[t];
+      reward += s >= 0 ? r[max(s, 0)] * cfg.stage_scales[0][max(s, 0)] * step_dt : xv[max(-1 - s, 0)];
+    }
   }
   if (blowup) {  // finite reward (the is_terminated term alone), the episode sums without this step
     reward = cfg.stage_scales[0][ZB_M_R_TERMINATION] * step_dt;
@@ -255,6 +356,10 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
       float* lr = log_row(q);
 #pragma unroll
       for (int t = 0; t < ZB_M_NUM_REWARD_TERMS; ++t) lr[t] = sums[t];
+      if constexpr (kTerms) {
+#pragma unroll
+        for (int t = 0; t < ZB_MT_NUM_TERMS; ++t) lr[ZB_M_NUM_REWARD_TERMS + t] = OUT(M_STG_TERMS + ZB_MT_EP_SUMS + t);
+      }
       lr[ACC_NRES] = 1.f;
       lr[ACC_DIED] = low ? 1.f : 0.f;
       lr[ACC_TOUT] = time_out ? 1.f : 0.f;
@@ -362,7 +467,14 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
       OUT(M_STG_EV + ZB_ME_HEADING_TARGET) = head_target;
       OUT(M_STG_EV + ZB_ME_IS_HEADING) = is_heading;
     }
+    if constexpr (kTerms) {  // ContactSensor.reset, reset_my_data and RewardManager.reset zero a reset env's rows
+      if (reset) {
+#pragma unroll
+        for (int f = 0; f < ZB_MT_STATE_DIM; ++f) OUT(M_STG_TERMS + f) = 0.f;
+      }
+    }
   }
   if constexpr (kEvents) m_ev_store(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, ev.st);
+  if constexpr (kTerms) m_terms_store(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, tm.st);
   step_finish<ZB_M_LINK_MU, ZB_M_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
 }

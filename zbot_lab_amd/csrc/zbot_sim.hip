@@ -4656,6 +4656,54 @@ __device__ __forceinline__ void m_write_obs(MP m, const zb_task_cfg& cfg, uint64
   for (int a = 0; a < ND; ++a) o[19 + a] = a_obs[a];
 }
 
+// ------------------------------------------------------------- the five more reward terms
+// include/zbot_manager_terms.h. zb_m_terms_step_kernel's extra arguments as one record (MEv's pattern):
+// the configuration and the side buffer (SoA [ZB_MT_STATE_DIM][N]).
+template <bool kTerms>
+struct MTerms {};
+template <>
+struct MTerms<true> {
+  const zb_manager_terms* c;  // device copy of the configuration: read in the reward epilogue only
+  float* st;
+};
+// the staging-row entries of the term state, after the event state
+constexpr int M_STG_TERMS = M_STG_EV + ZB_ME_STATE_DIM;
+static_assert(M_STG_TERMS + ZB_MT_STATE_DIM <= STG_LEN && ZB_MT_STATE_DIM <= WGT / EPW, "staging row");
+static_assert(ZB_M_NUM_REWARD_TERMS + ZB_MT_NUM_TERMS <= ZB_MAX_REWARD_TERMS, "episode-log slots 11..15");
+// RewardsCfg field order (zbotlab_env_cfg.py:261-366 without undesired_contacts): t >= 0 the compiled
+// term zb_manager_reward_term t, t < 0 the extra term -1 - t
+__device__ constexpr int M_CFG_ORDER[ZB_M_NUM_REWARD_TERMS + ZB_MT_NUM_TERMS] = {
+    ZB_M_R_TRACK_LIN_VEL_XY, ZB_M_R_TRACK_ANG_VEL_Z, ZB_M_R_TERMINATION, ZB_M_R_DOF_TORQUES, ZB_M_R_DOF_ACC,
+    ZB_M_R_ACTION_RATE, ZB_M_R_FOOT_STEP_LENGTH, ZB_M_R_FOOT_DOWNWARD, ZB_M_R_FOOT_FORWARD, -1 - ZB_MT_GAIT,
+    ZB_M_R_FEET_SLIDE, -1 - ZB_MT_FEET_CLEARANCE, -1 - ZB_MT_FEET_AIR_TIME, ZB_M_R_AIR_TIME_BALANCE,
+    -1 - ZB_MT_BASE_VEL_FORWARD, -1 - ZB_MT_FEET_FORCE_PATTERN};
+
+// the term state into the carry rows behind the event state, in the prologue's load batch: lane s of the
+// team loads row s (carry_prefetch has zeroed these entries; the wave's LDS writes land in program order)
+constexpr int M_CST_TERMS = ZB_M_LINK_MU + ZB_ME_STATE_DIM;
+static_assert(M_CST_TERMS + ZB_MT_STATE_DIM - CARRY0 <= CARRY_W && ZB_MT_STATE_DIM <= TL, "carry width");
+__device__ __forceinline__ void m_terms_prefetch(const Q& q, int N, int i, const float* __restrict__ ts) {
+  if (q.s < ZB_MT_STATE_DIM) q.carry()[M_CST_TERMS - CARRY0 + q.s] = ts[(size_t)q.s * N + i];
+}
+
+// x mod y for x >= 0, y > 0 and x / y < 2^22, exact like fmodf and without its data-dependent loop: the
+// quotient from the approximate division is off by at most one, the fused remainder is exact, and two
+// selects put it back into [0, y)
+__device__ __forceinline__ float fmod_pos(float x, float y) {
+  float r = fmaf(-floorf(x / y), y, x);
+  r = r < 0.f ? r + y : r;
+  return r >= y ? r - y : r;
+}
+
+// the term-state entries of the staging row out to the side buffer: one store of the wave (m_ev_store)
+__device__ __forceinline__ void m_terms_store(const Q& q, int env0, int N, float* __restrict__ ts) {
+  wave_sync();
+  const float* S = reinterpret_cast<const float*>(q.b + YG_OFF);
+  const int e = q.lane % EPW, f0 = q.lane / EPW;
+  const int env = env0 + e;
+  if (env < N && f0 < ZB_MT_STATE_DIM) ts[(size_t)f0 * N + env] = S[e * STG_LEN + M_STG_TERMS + f0];
+}
+
 struct PreM {
   float delta[ND], jqd_prev[ND], a_raw[ND], action_rate;
 };
@@ -4668,6 +4716,8 @@ static_assert(sizeof(PreM) <= 16 * PRE4, "PreM fits PRE4 granules");
 #define ZB_M_EV_INIT {}
 #define ZB_M_BI 0
 #define ZB_M_BI_ROWS static_cast<const float4*>(nullptr)
+#define ZB_M_TERMS 0
+#define ZB_M_TERMS_INIT {}
 #include "zbot_m_step.inc"
 #undef ZB_M_STEP_KERNEL
 #undef ZB_M_EVENTS
@@ -4689,11 +4739,82 @@ static_assert(sizeof(PreM) <= 16 * PRE4, "PreM fits PRE4 granules");
 #define ZB_M_BI_ROWS bi
 #include "zbot_m_step.inc"
 #undef ZB_M_STEP_KERNEL
+#undef ZB_M_EV_PARAMS
+#undef ZB_M_TERMS
+#undef ZB_M_TERMS_INIT
+// the dr build with the five more reward terms (include/zbot_manager_terms.h)
+#define ZB_M_STEP_KERNEL zb_m_terms_step_kernel
+#define ZB_M_EV_PARAMS \
+  zb_manager_events evc, float* __restrict__ evst, const float4* __restrict__ bi, const zb_manager_terms* __restrict__ tmc, \
+      float* __restrict__ tmst,
+#define ZB_M_TERMS 1
+#define ZB_M_TERMS_INIT {tmc, tmst}
+#include "zbot_m_step.inc"
+#undef ZB_M_STEP_KERNEL
 #undef ZB_M_EVENTS
 #undef ZB_M_EV_PARAMS
 #undef ZB_M_EV_INIT
 #undef ZB_M_BI
 #undef ZB_M_BI_ROWS
+#undef ZB_M_TERMS
+#undef ZB_M_TERMS_INIT
+
+// zb_set_manager_terms: the configuration into its device copy, in stream order (no host-side staging)
+__global__ void zb_m_terms_cfg_kernel(zb_manager_terms tc, zb_manager_terms* __restrict__ dst) { *dst = tc; }
+
+// explicit resets while the terms are on (zb_reset; beside zb_m_reset_kernel, which does not change): the
+// five episode sums into the log accumulator (init: none), then the env's rows zeroed (ContactSensor.reset,
+// reset_my_data, RewardManager.reset); one thread per env
+__global__ void zb_m_terms_reset_kernel(int N, const int32_t* __restrict__ ids, int n, float* __restrict__ acc, int init,
+                                        float* __restrict__ ts) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int i = ids ? ids[t] : t;
+  if (i < 0 || i >= N) return;
+  if (!init) {
+#pragma unroll
+    for (int k = 0; k < ZB_MT_NUM_TERMS; ++k)
+      atomicAdd(&acc_slot(acc, t)[ZB_M_NUM_REWARD_TERMS + k], ts[(size_t)(ZB_MT_EP_SUMS + k) * N + i]);
+  }
+#pragma unroll
+  for (int f = 0; f < ZB_MT_STATE_DIM; ++f) ts[(size_t)f * N + i] = 0.f;
+}
+
+// zb_get_manager_terms_state: the state rows, then the terms' inputs on the current state by the
+// out-of-line kinematics (fk / body_vel, as the observation kernels): one thread per env
+__global__ void zb_m_terms_get_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
+                                      const float* __restrict__ ts, zb_manager_terms tc, float* __restrict__ out) {
+  MP m = to_mp(mg);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+#pragma unroll
+  for (int f = 0; f < ZB_MT_STATE_DIM; ++f) out[(size_t)f * N + i] = ts[(size_t)f * N + i];
+  Phys p;
+  load_phys(st, N, i, p);
+  Kin k;
+  fk(m, p, k);
+  float V[NB][6];
+  body_vel(k, p, V);
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int l = f == 0 ? 0 : 11, b = link_body(l);
+    float c[3], v[3];
+    mv3(k.R[b], tc.clearance_point[f], c);
+    out[(size_t)(ZB_MT_D_FOOT_Z + f) * N + i] = p.pos[2] + k.p[b][2] + c[2];
+    link_com_vel(m, k, V, l, v);
+    out[(size_t)(ZB_MT_D_FOOT_VXY + 2 * f) * N + i] = v[0];
+    out[(size_t)(ZB_MT_D_FOOT_VXY + 2 * f + 1) * N + i] = v[1];
+  }
+  float bp[3], bq[4], Rb[9], wc[3];
+  link_pose(m, k, m->base_link, bp, bq);
+  qmat(bq, Rb);
+  out[(size_t)ZB_MT_D_FWD_XY * N + i] = Rb[4];
+  out[(size_t)(ZB_MT_D_FWD_XY + 1) * N + i] = -Rb[1];
+  constexpr int b = link_body(6);  // (the base link's body: critic_tail)
+  cross3(V[b], bp, wc);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[(size_t)(ZB_MT_D_ROOT_VEL + a) * N + i] = V[b][3 + a] + wc[a];
+}
 
 // ------------------------------------------------------------- per-env base mass and COM
 // include/zbot_base_inertia.h. The side buffer is float4[N][4]: the base composite body's three table
@@ -5222,6 +5343,12 @@ struct zb_sim {
   int* d_bi_flag = nullptr;
   zb_base_link base_link = {};
   bool bi_on = false;
+  // manager task, include/zbot_manager_terms.h: the configuration, the side buffer (ZB_MT_STATE_DIM x n,
+  // allocated by zb_create) and whether a term is active (the terms kernel)
+  zb_manager_terms tm = {};
+  float* d_tm = nullptr;
+  zb_manager_terms* d_tmc = nullptr;  // the step kernel reads the configuration from here
+  bool tm_on = false;
 };
 
 static thread_local char g_err[512] = "";
@@ -5297,6 +5424,7 @@ static void reset_v4(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, in
 static void reset_m(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, int init) {
   zb_m_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state, ids, cnt, h->d_acc,
                                                       h->d_cnt, h->seed, init, h->ev, h->ev_on ? h->d_ev : nullptr);
+  if (h->tm_on) zb_m_terms_reset_kernel<<<(cnt + 255) / 256, 256, 0, s>>>(h->n, ids, cnt, h->d_acc, init, h->d_tm);
 }
 static int init_v2(zb_handle h) { reset_v2(h, nullptr, h->n, 0, 1); return launch_check("zb_reset_kernel"); }
 static int init_su(zb_handle h) {
@@ -5370,6 +5498,13 @@ static void with_variant(const StepVariant& v, F&& f) {
     if (v.rf) return v.tgs ? occ(T{}, N{}, T{}) : occ(N{}, N{}, T{});
   }
   return v.tgs ? occ(T{}, N{}, N{}) : occ(N{}, N{}, N{});
+}
+
+// The manager task's build of the step kernel's text: what zb_step launches and zb_kernel_variant_name
+// reports. The terms build has the events and the base inertia compiled in, the dr build the events.
+enum class MBuild { plain, events, dr, terms };
+static MBuild m_build(const zb_sim* h) {
+  return h->tm_on ? MBuild::terms : h->bi_on ? MBuild::dr : h->ev_on ? MBuild::events : MBuild::plain;
 }
 
 extern "C" {
@@ -5559,6 +5694,11 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
     HIPCHK(hipMemcpy(h->d_bi, rows.data(), sizeof(float4) * rows.size(), hipMemcpyHostToDevice), "hipMemcpy base inertia");
     HIPCHK(hipMalloc(&h->d_bi_flag, sizeof(int)), "hipMalloc base inertia flag");
     HIPCHK(hipMemset(h->d_bi_flag, 0, sizeof(int)), "hipMemset base inertia flag");
+    // the term state (include/zbot_manager_terms.h): zero while no term is active
+    HIPCHK(hipMalloc(&h->d_tm, sizeof(float) * ZB_MT_STATE_DIM * (size_t)num_envs), "hipMalloc term state");
+    HIPCHK(hipMemset(h->d_tm, 0, sizeof(float) * ZB_MT_STATE_DIM * (size_t)num_envs), "hipMemset term state");
+    HIPCHK(hipMalloc(&h->d_tmc, sizeof(zb_manager_terms)), "hipMalloc term cfg");
+    HIPCHK(hipMemset(h->d_tmc, 0, sizeof(zb_manager_terms)), "hipMemset term cfg");
   }
   HIPCHK(hipDeviceSynchronize(), "zb_create sync");
   *out = h;
@@ -5669,6 +5809,8 @@ void zb_destroy(zb_handle h) {
   (void)hipFree(h->d_wc);
   (void)hipFree(h->d_ev);
   (void)hipFree(h->d_bi);
+  (void)hipFree(h->d_tm);
+  (void)hipFree(h->d_tmc);
   (void)hipFree(h->d_bi_flag);
   (void)hipFree(h->d_acc);
   (void)hipFree(h->d_cnt);
@@ -5739,8 +5881,11 @@ int zb_step(zb_handle h, const float* actions, float* obs, float* reward, uint8_
   else if (h->task == ZB_TASK_MANAGER_V0)
     with_variant<false>(v, [&](auto t, auto o, auto, auto) {
       // (events off: h->ev holds nothing enabled, so the dr build draws and pushes nothing more)
-      if (h->bi_on) go(zb_m_dr_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev, h->d_bi);
-      else if (h->ev_on) go(zb_m_events_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev);
+      const MBuild b = m_build(h);
+      if (b == MBuild::terms)
+        go(zb_m_terms_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev, h->d_bi, h->d_tmc, h->d_tm);
+      else if (b == MBuild::dr) go(zb_m_dr_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev, h->d_bi);
+      else if (b == MBuild::events) go(zb_m_events_step_kernel<t.value, o.value>, h->d_cnt, h->seed, h->ev, h->d_ev);
       else go(zb_m_step_kernel<t.value, o.value>, h->d_cnt, h->seed);
     });
   else
@@ -5863,6 +6008,59 @@ int zb_set_manager_event_state(zb_handle h, const float* src, void* stream) {
   HIPCHK(hipMemcpyAsync(h->d_ev, src, sizeof(float) * ZB_ME_STATE_DIM * (size_t)h->n, hipMemcpyDeviceToDevice,
                         (hipStream_t)stream),
          "hipMemcpyAsync event state");
+  return 0;
+}
+
+int zb_set_manager_terms(zb_handle h, const zb_manager_terms* tc, void* stream) {
+  if (!h || !tc) return set_err(-1, "zb_set_manager_terms", hipSuccess);
+  if (h->task != ZB_TASK_MANAGER_V0)
+    return set_err(-1, "zb_set_manager_terms: gait, feet_clearance, feet_air_time, base_vel_forward and "
+                       "feet_force_pattern are manager-task reward terms", hipSuccess);
+  bool ok = (tc->active >> ZB_MT_NUM_TERMS) == 0u;
+  for (int k = 0; k < ZB_MT_NUM_TERMS; ++k) {  // finite, on the bits (-ffast-math folds isfinite away)
+    uint32_t u;
+    memcpy(&u, &tc->weight[k], sizeof(u));
+    ok = ok && (u & 0x7f800000u) != 0x7f800000u;
+  }
+  if (tc->active)
+    ok = ok && tc->gait_period > 0.f && tc->clearance_std > 0.f && (tc->which_forward == 1.f || tc->which_forward == -1.f);
+  if (!ok)
+    return set_err(-1, "zb_set_manager_terms: active bits 0..4, finite weights, gait_period > 0, clearance_std > 0, "
+                       "which_forward +-1", hipSuccess);
+  h->tm = *tc;
+  h->tm_on = tc->active != 0u;
+  HIPCHK(hipMemsetAsync(h->d_tm, 0, sizeof(float) * ZB_MT_STATE_DIM * (size_t)h->n, (hipStream_t)stream), "hipMemsetAsync term state");
+  zb_m_terms_cfg_kernel<<<1, 1, 0, (hipStream_t)stream>>>(h->tm, h->d_tmc);
+  if (launch_check("zb_m_terms_cfg_kernel")) return -1;
+  return 0;
+}
+
+int zb_manager_terms_active(zb_handle h) { return h && h->tm_on ? 1 : 0; }
+
+const char* zb_kernel_variant_name(zb_handle h) {
+  if (!h) return nullptr;
+  if (h->task == ZB_TASK_STANDUP_V0) return "zb_su_step_kernel";
+  if (h->task == ZB_TASK_WALKING_V4) return "zb_v4_step_kernel";
+  if (h->task != ZB_TASK_MANAGER_V0) return "zb_step_kernel";
+  switch (m_build(h)) {
+    case MBuild::terms: return "zb_m_terms_step_kernel";
+    case MBuild::dr: return "zb_m_dr_step_kernel";
+    case MBuild::events: return "zb_m_events_step_kernel";
+    default: return "zb_m_step_kernel";
+  }
+}
+
+int zb_get_manager_terms_state(zb_handle h, float* dst, void* stream) {
+  if (!h || !dst || !h->d_tm) return set_err(-1, "zb_get_manager_terms_state (a manager-task handle)", hipSuccess);
+  zb_m_terms_get_kernel<<<(h->n + 63) / 64, 64, 0, (hipStream_t)stream>>>(h->d_model, h->n, h->d_state, h->d_tm, h->tm, dst);
+  return launch_check("zb_m_terms_get_kernel");
+}
+
+int zb_set_manager_terms_state(zb_handle h, const float* src, void* stream) {
+  if (!h || !src || !h->d_tm) return set_err(-1, "zb_set_manager_terms_state (a manager-task handle)", hipSuccess);
+  HIPCHK(hipMemcpyAsync(h->d_tm, src, sizeof(float) * ZB_MT_STATE_DIM * (size_t)h->n, hipMemcpyDeviceToDevice,
+                        (hipStream_t)stream),
+         "hipMemcpyAsync term state");
   return 0;
 }
 

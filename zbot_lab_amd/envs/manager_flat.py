@@ -122,9 +122,40 @@ def _feet(p=None):
     return dict({"asset_cfg": "robot:foot.*"}, **(p or {}))
 
 
+def base_reward_term(name: str) -> RewTerm:
+    """The reference's base cfg's term for one of the five fields the flat cfg sets to ``None``
+    (zbotlab_env_cfg.py:301-366: func, weight and params), e.g. ``cfg.rewards.gait = base_reward_term("gait")``."""
+    sensor = {"sensor_cfg": "contact_forces:foot.*"}
+    terms = {
+        "gait": lambda: RewTerm("feet_gait", 0.5, dict(
+            {"period": 2.0, "offset": [0.0, 0.5], "threshold": 0.55, "command_name": "base_velocity"}, **sensor)),
+        "feet_clearance": lambda: RewTerm("foot_clearance_reward", 1.0, _feet(
+            {"std": 0.05, "tanh_mult": 2.0, "target_height": 0.01})),
+        "feet_air_time": lambda: RewTerm("feet_air_time_positive_biped", 2.5, dict(
+            {"command_name": "base_velocity", "threshold": 0.3}, **sensor)),
+        "base_vel_forward": lambda: RewTerm("base_vel_forward", 1.0, {"which_forward": 1}),
+        "feet_force_pattern": lambda: RewTerm("feet_force_pattern", 1.0, dict(sensor)),
+    }
+    if name not in terms:
+        raise KeyError(f"{name!r} is not one of {zm.M_EXTRA_REWARD_TERMS}")
+    return terms[name]()
+
+
+_TERMS_COMPILED = (
+    "compiled: rewards.gait = RewTerm('feet_gait', w, {'period': > 0, 'offset': [o0, o1], 'threshold': t, "
+    "'command_name': 'base_velocity', 'sensor_cfg': 'contact_forces:foot.*'}); rewards.feet_clearance = RewTerm("
+    "'foot_clearance_reward', w, {'std': > 0, 'tanh_mult': m, 'target_height': h, 'asset_cfg': 'robot:foot.*'}); "
+    "rewards.feet_air_time = RewTerm('feet_air_time_positive_biped', w, {'command_name': 'base_velocity', "
+    "'threshold': t, 'sensor_cfg': 'contact_forces:foot.*'}); rewards.base_vel_forward = RewTerm('base_vel_forward', "
+    "w, {'which_forward': 1 | -1}); rewards.feet_force_pattern = RewTerm('feet_force_pattern', w, {'sensor_cfg': "
+    "'contact_forces:foot.*'}); beside any subset of the flat cfg's 11 terms with their own func / params. "
+    "rewards.undesired_contacts and terminations.base_contact (net contact forces on non-foot links) are not compiled")
+
+
 @dataclass
 class RewardsCfg:
-    """mgr.py:261-377 after flat_env_cfg.py:169-182 (weights 5.0 / -6.5 / -15.0, six terms None)."""
+    """mgr.py:261-377 after flat_env_cfg.py:169-182 (weights 5.0 / -6.5 / -15.0, six terms None; five of
+    the six compile when restored: ``base_reward_term``)."""
     track_lin_vel_xy_exp: RewTerm | None = field(default_factory=lambda: RewTerm(
         "track_lin_vel_xy_yaw_frame_exp", 1.0, {"command_name": "base_velocity", "std": math.sqrt(0.25)}))
     track_ang_vel_z_exp: RewTerm | None = field(default_factory=lambda: RewTerm(
@@ -250,20 +281,30 @@ class Zbot6BFlatEnvCfg:
     def reward_cfg(self) -> dict:
         return {"reward_scales": {k: t.weight for k, t in _active(self.rewards)}}
 
+    def reward_terms(self) -> list:
+        """The active reward terms' names in cfg order (the ``Episode_Reward/*`` keys)."""
+        return [k for k, _ in _active(self.rewards)]
+
     def task_cfg(self) -> zm.TaskCfg:
-        """Compile the manager cfg into the kernel's task parameters (raises on unsupported terms)."""
-        rew = _active(self.rewards)
+        """Compile the manager cfg into the kernel's task parameters (raises on unsupported terms). Any of
+        the flat cfg's 11 terms may be ``None`` (weight 0 in the kernel); the five restored terms compile
+        beside it (``manager_terms()``)."""
+        rew = [(k, t) for k, t in _active(self.rewards) if k not in zm.M_EXTRA_REWARD_TERMS]
         names = [k for k, _ in rew]
-        if names != zm.M_REWARD_TERMS:
-            raise NotImplementedError(f"reward terms {names} != the compiled set {zm.M_REWARD_TERMS}")
+        if not set(names) <= set(zm.M_REWARD_TERMS):
+            raise NotImplementedError(f"reward terms {sorted(set(names) - set(zm.M_REWARD_TERMS))} are not compiled; "
+                                      f"{_TERMS_COMPILED}")
         expect = RewardsCfg()
         for k, t in rew:
             ref = getattr(expect, k)
             if t.func != ref.func or t.params != ref.params:
                 raise NotImplementedError(f"reward term {k}: func / params {t.func} {t.params} not compiled")
+        self.manager_terms()  # gait, feet_clearance, feet_air_time, base_vel_forward, feet_force_pattern
         term = _active(self.terminations)
         if [k for k, _ in term] != zm.M_TERMINATION_TERMS:
-            raise NotImplementedError(f"termination terms {[k for k, _ in term]} != {zm.M_TERMINATION_TERMS}")
+            extra = " (terminations.base_contact needs net contact forces on non-foot links; " + _TERMS_COMPILED + ")" \
+                if any(k == "base_contact" for k, _ in term) else ""
+            raise NotImplementedError(f"termination terms {[k for k, _ in term]} != {zm.M_TERMINATION_TERMS}{extra}")
         cmd = self.commands.base_velocity
         self.manager_events()  # push_robot, ang_vel_z, heading_command: raises on the forms not compiled
         lo, hi = cmd.resampling_time_range
@@ -346,6 +387,59 @@ class Zbot6BFlatEnvCfg:
             out.heading_command, out.cmd_heading = True, hd
             out.cmd_rel_heading = float(cmd.rel_heading_envs)
             out.heading_stiffness = float(cmd.heading_control_stiffness)
+        return out
+
+    def manager_terms(self) -> zm.ManagerTerms:
+        """Compile ``rewards.gait`` / ``feet_clearance`` / ``feet_air_time`` / ``base_vel_forward`` /
+        ``feet_force_pattern`` into the kernel's term parameters (``zb_set_manager_terms``; they live beside
+        ``TaskCfg``, which they leave unchanged). The unedited cfg gives "none active". Raises
+        ``NotImplementedError`` on a form that is not compiled, saying what is."""
+        out = zm.ManagerTerms()
+        r = self.rewards
+
+        def params_of(name, func, keys, fixed):
+            t = getattr(r, name)
+            p = t.params if isinstance(t.params, dict) else None
+            if t.func != func or p is None or set(p) != set(keys) | set(fixed) or any(p[k] != v for k, v in fixed.items()):
+                raise NotImplementedError(f"rewards.{name}: {t.func!r} / {t.params!r} is not compiled; {_TERMS_COMPILED}")
+            out.weights[name] = float(t.weight)
+            return p
+
+        def number(name, key, v, positive=False):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or (positive and not v > 0):
+                raise NotImplementedError(f"rewards.{name}: {key} = {v!r} is not compiled; {_TERMS_COMPILED}")
+            return float(v)
+
+        if r.undesired_contacts is not None:
+            raise NotImplementedError("rewards.undesired_contacts needs net contact forces on non-foot links (ground and "
+                                      f"self contact, 3-slot history) and is not compiled; {_TERMS_COMPILED}")
+        sensor = {"sensor_cfg": "contact_forces:foot.*"}
+        if r.gait is not None:
+            p = params_of("gait", "feet_gait", ("period", "offset", "threshold"), dict(sensor, command_name="base_velocity"))
+            off = p["offset"]
+            if not isinstance(off, (list, tuple)) or len(off) != 2:
+                raise NotImplementedError(f"rewards.gait: offset = {off!r} needs one entry per foot; {_TERMS_COMPILED}")
+            out.gait_period = number("gait", "period", p["period"], positive=True)
+            out.gait_offset = tuple(number("gait", "offset", v) for v in off)
+            out.gait_threshold = number("gait", "threshold", p["threshold"])
+        if r.feet_clearance is not None:
+            p = params_of("feet_clearance", "foot_clearance_reward", ("std", "tanh_mult", "target_height"),
+                          {"asset_cfg": "robot:foot.*"})
+            out.clearance_std = number("feet_clearance", "std", p["std"], positive=True)
+            out.clearance_tanh_mult = number("feet_clearance", "tanh_mult", p["tanh_mult"])
+            out.clearance_target_height = number("feet_clearance", "target_height", p["target_height"])
+        if r.feet_air_time is not None:
+            p = params_of("feet_air_time", "feet_air_time_positive_biped", ("threshold",),
+                          dict(sensor, command_name="base_velocity"))
+            out.air_time_threshold = number("feet_air_time", "threshold", p["threshold"])
+        if r.base_vel_forward is not None:
+            p = params_of("base_vel_forward", "base_vel_forward", ("which_forward",), {})
+            if isinstance(p["which_forward"], bool) or p["which_forward"] not in (1, -1):
+                raise NotImplementedError(f"rewards.base_vel_forward: which_forward = {p['which_forward']!r} must be "
+                                          f"1 or -1; {_TERMS_COMPILED}")
+            out.which_forward = int(p["which_forward"])
+        if r.feet_force_pattern is not None:
+            params_of("feet_force_pattern", "feet_force_pattern", (), sensor)
         return out
 
     def base_inertia(self) -> "BaseInertiaEvents":
@@ -506,6 +600,9 @@ class ZbotManagerBasedRLEnv(ZbotDirectEnvV2):
         if events.enabled:  # right after construction, before the first reset: construction semantics
             self.sim.set_manager_events(events)
         self._startup_base_inertia()
+        terms = self.cfg.manager_terms()
+        if terms.enabled:  # init_my_data: feet_force_sum, the contact timers and the five sums start at zero
+            self.sim.set_manager_terms(terms)
         ev = self.cfg.events.physics_material
         if ev is None:
             return
@@ -536,7 +633,7 @@ class ZbotManagerBasedRLEnv(ZbotDirectEnvV2):
         if getattr(self, "_log", None) is None:
             means, counts = self.sim.read_log()
             buf = self.sim.log_buffer
-            log = {f"Episode_Reward/{k}": means[i] for i, k in enumerate(zm.M_REWARD_TERMS)}
+            log = {f"Episode_Reward/{k}": buf[zm.m_log_slot(k)] for k in self.cfg.reward_terms()}
             if self.cfg.curriculum.lin_vel_cmd_levels is not None:
                 log["Curriculum/lin_vel_cmd_levels"] = buf[16]
             log["Metrics/base_velocity/error_vel_xy"] = buf[17]

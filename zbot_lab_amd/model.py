@@ -205,6 +205,76 @@ class ManagerEvents:
         return e
 
 
+# The five reward terms of the reference's base cfg that the flat cfg sets to None and a cfg may restore
+# (include/zbot_manager_terms.h enum zb_manager_extra_term; Episode_Reward log slots 11..15), and the
+# RewardsCfg field order of the sixteen compiled terms (zbotlab_env_cfg.py:261-366).
+M_EXTRA_REWARD_TERMS = ["gait", "feet_clearance", "feet_air_time", "base_vel_forward", "feet_force_pattern"]
+M_REWARD_FIELD_ORDER = [
+    "track_lin_vel_xy_exp", "track_ang_vel_z_exp", "termination_penalty", "dof_torques_l2", "dof_acc_l2",
+    "action_rate_l2", "foot_step_length", "foot_downward", "foot_forward", "gait", "feet_slide", "feet_clearance",
+    "feet_air_time", "air_time_variance", "base_vel_forward", "feet_force_pattern",
+]
+# rows of the term state (enum zb_manager_terms_state_field) and of what the getter appends
+MT = dict(CONTACT_CUR=0, FEET_FORCE_SUM=2, EP_SUMS=3, D_FOOT_Z=8, D_FOOT_VXY=10, D_FWD_XY=14, D_ROOT_VEL=16)
+MT_STATE_DIM, MT_GET_DIM = 8, 19
+
+
+def m_log_slot(name: str) -> int:
+    """The Episode_Reward slot of a manager reward term in the episode log (zb_read_log)."""
+    if name in M_REWARD_TERMS:
+        return M_REWARD_TERMS.index(name)
+    return M_NUM_TERMS + M_EXTRA_REWARD_TERMS.index(name)
+
+
+class ZbManagerTerms(C.Structure):
+    """include/zbot_manager_terms.h ``zb_manager_terms``."""
+    _fields_ = [
+        ("active", C.c_uint32), ("weight", C.c_float * 5), ("gait_period", C.c_float), ("gait_offset", C.c_float * 2),
+        ("gait_threshold", C.c_float), ("clearance_std", C.c_float), ("clearance_tanh_mult", C.c_float),
+        ("clearance_target_height", C.c_float), ("clearance_point", (C.c_float * 3) * 2),
+        ("air_time_threshold", C.c_float), ("which_forward", C.c_float),
+    ]
+
+
+@dataclass
+class ManagerTerms:
+    """The manager task's five more reward terms (``zb_set_manager_terms``): what
+    ``Zbot6BFlatEnvCfg.manager_terms()`` compiles ``rewards.gait`` / ``feet_clearance`` / ``feet_air_time`` /
+    ``base_vel_forward`` / ``feet_force_pattern`` into. ``weights`` holds the active terms only; the
+    default is "none active"."""
+    weights: dict = field(default_factory=dict)
+    gait_period: float = 2.0
+    gait_offset: tuple = (0.0, 0.5)
+    gait_threshold: float = 0.55
+    clearance_std: float = 0.05
+    clearance_tanh_mult: float = 2.0
+    clearance_target_height: float = 0.01
+    air_time_threshold: float = 0.3
+    which_forward: int = 1
+
+    @property
+    def enabled(self) -> bool:
+        return bool(self.weights)
+
+    def pack(self, robot: "RobotModel") -> ZbManagerTerms:
+        t = ZbManagerTerms()
+        for k, name in enumerate(M_EXTRA_REWARD_TERMS):
+            if name in self.weights:
+                t.active |= 1 << k
+                t.weight[k] = float(self.weights[name])
+        t.gait_period = float(self.gait_period)
+        t.gait_offset[:] = [float(v) for v in self.gait_offset]
+        t.gait_threshold = float(self.gait_threshold)
+        t.clearance_std = float(self.clearance_std)
+        t.clearance_tanh_mult = float(self.clearance_tanh_mult)
+        t.clearance_target_height = float(self.clearance_target_height)
+        for f, l in enumerate((0, NUM_LINKS - 1)):  # the feet links' COM, body frame (zb_model.link_com)
+            t.clearance_point[f][:] = [float(v) for v in robot.link_com[l]]
+        t.air_time_threshold = float(self.air_time_threshold)
+        t.which_forward = float(self.which_forward)
+        return t
+
+
 # ----------------------------------------------------------------------------- math helpers
 def qmul(a, b):
     aw, ax, ay, az = a

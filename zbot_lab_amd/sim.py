@@ -226,6 +226,42 @@ class ZbotSim:
         nat.check(self.lib.zb_get_base_link_com(self._h, nat.ptr(out), _stream(self.device)), "zb_get_base_link_com")
         return out
 
+    # ------------------------------------------------------------------ the five more reward terms
+    def set_manager_terms(self, terms: zm.ManagerTerms) -> None:
+        """Manager task: activate gait / feet_clearance / feet_air_time / base_vel_forward /
+        feet_force_pattern (zb_set_manager_terms; include/zbot_manager_terms.h). Zeroes the contact timers,
+        the integrator and the five episode sums: call it right after construction."""
+        self._terms = terms.pack(self.robot)
+        nat.check(self.lib.zb_set_manager_terms(self._h, C.byref(self._terms), _stream(self.device)),
+                  "zb_set_manager_terms")
+
+    @property
+    def terms_active(self) -> bool:
+        """Whether the next step launches zb_m_terms_step_kernel."""
+        return bool(self.lib.zb_manager_terms_active(self._h))
+
+    def kernel_name(self) -> str:
+        """The step kernel the next step() launches, by name (zb_kernel_variant_name; kernel_variant()
+        gives its template arguments)."""
+        return self.lib.zb_kernel_variant_name(self._h).decode()
+
+    def get_terms_state(self) -> torch.Tensor:
+        """[MT_GET_DIM, N]: the term state (contact timers, feet_force_sum, the five episode sums), then the
+        terms' inputs on the current state (feet clearance heights and COM velocities, the forward vector,
+        the root link's velocity); rows in ``model.MT``."""
+        out = torch.empty(zm.MT_GET_DIM, self.num_envs, dtype=torch.float32, device=self.device)
+        nat.check(self.lib.zb_get_manager_terms_state(self._h, nat.ptr(out), _stream(self.device)),
+                  "zb_get_manager_terms_state")
+        return out
+
+    def set_terms_state(self, ts: torch.Tensor) -> None:
+        t = ts.to(device=self.device, dtype=torch.float32).contiguous()
+        if t.shape != (zm.MT_STATE_DIM, self.num_envs):
+            raise ValueError(f"term state must be [{zm.MT_STATE_DIM}, {self.num_envs}]")
+        nat.check(self.lib.zb_set_manager_terms_state(self._h, nat.ptr(t), _stream(self.device)),
+                  "zb_set_manager_terms_state")
+        torch.cuda.current_stream(self.device).synchronize()  # `t` may be a temporary
+
     def set_log_accumulator(self, acc: torch.Tensor | None) -> None:
         """Register a device float[ZB_LOG_LEN + ZB_LOG_COUNTS] accumulator that every later step adds the
         log's current values to inside its finalize launch (zb_set_log_accumulator; the PPO runner's
