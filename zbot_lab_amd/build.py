@@ -21,6 +21,22 @@ def hipcc() -> str:
 
 
 STAMPS_OUT = os.path.join(HERE, "libzbot_stamps.so")
+PPO_SRC = os.path.join(HERE, "csrc", "ppo_mlp.hip")
+PPO_OUT = os.path.join(HERE, "libzbot_ppo.so")
+
+
+def sim_deps() -> list:
+    """What libzbot.so is built from: zbot_sim.hip, every piece under csrc/, sub-folders included (all
+    but the PPO source), every header under include/, and this file."""
+    csrc, inc = os.path.dirname(SRC), os.path.join(ROOT, "include")
+    pieces = sorted(os.path.join(d, f) for d, _, fs in os.walk(csrc) for f in fs if f.endswith((".h", ".inc", ".hip")))
+    headers = [os.path.join(inc, f) for f in sorted(os.listdir(inc)) if f.endswith(".h")]
+    return [SRC] + [f for f in pieces if f not in (SRC, PPO_SRC)] + headers + [os.path.abspath(__file__)]
+
+
+def ppo_deps() -> list:
+    """What libzbot_ppo.so is built from: ppo_mlp.hip, its header, and this file."""
+    return [PPO_SRC, os.path.join(ROOT, "include", "zbot_ppo.h"), os.path.abspath(__file__)]
 
 
 def build(force: bool = False, verbose: bool = False, stamps: bool = False, defines: tuple = (),
@@ -28,11 +44,7 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False, defi
     """defines / out: an experiment variant (e.g. ``-DZB_GJK_TOL=3e-5f`` into ``libzbot_x.so``),
     selected at run time with ZBOT_LIB=<file name>."""
     out = os.path.join(HERE, out) if out else (STAMPS_OUT if stamps else OUT)
-    deps = [SRC, os.path.join(HERE, "csrc", "zbot_m_step.inc"), os.path.join(ROOT, "include", "zbot.h"), os.path.join(ROOT, "include", "zbot_critic_obs.h"),
-            os.path.join(ROOT, "include", "zbot_manager_events.h"), os.path.join(ROOT, "include", "zbot_base_inertia.h"),
-            os.path.join(ROOT, "include", "zbot_manager_terms.h"),
-            os.path.abspath(__file__)]
-    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
+    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in sim_deps()):
         return out
     # -fno-slp-vectorize: packing scalar f32 math into v_pk_* pairs forces aligned register pairs
     # and shuffles; on this register-bound kernel it costs ~1.1 KB/lane of scratch spills.
@@ -58,15 +70,10 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False, defi
     return out
 
 
-PPO_SRC = os.path.join(HERE, "csrc", "ppo_mlp.hip")
-PPO_OUT = os.path.join(HERE, "libzbot_ppo.so")
-
-
 def build_ppo(force: bool = False) -> str:
     """libzbot_ppo.so: the fused PPO minibatch update (fp32 MFMA, include/zbot_ppo.h). Plain -O3:
     no fast-math (expf / logf / division as torch computes them)."""
-    deps = [PPO_SRC, os.path.join(ROOT, "include", "zbot_ppo.h"), os.path.abspath(__file__)]
-    if not force and os.path.exists(PPO_OUT) and all(os.path.getmtime(PPO_OUT) >= os.path.getmtime(d) for d in deps):
+    if not force and os.path.exists(PPO_OUT) and all(os.path.getmtime(PPO_OUT) >= os.path.getmtime(d) for d in ppo_deps()):
         return PPO_OUT
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"),
            "-o", PPO_OUT + ".tmp", PPO_SRC]

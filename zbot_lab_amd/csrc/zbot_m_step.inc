@@ -1,22 +1,32 @@
-// The manager step kernel's text, stamped twice by zbot_sim.hip: as zb_m_step_kernel (ZB_M_EVENTS 0: the
-// kernel as it was before the events existed, same name, arguments and instructions) and as
-// zb_m_events_step_kernel (ZB_M_EVENTS 1: the interval push and the yaw / heading commands of
-// include/zbot_manager_events.h compiled in; two more arguments, the configuration and the event-state
-// side buffer). One text, so the two cannot drift; two kernels, because a shared __device__ body does
-// not reproduce the events-off code (profiles/manager_events/kernel_resources.txt).
-// A third stamp, zb_m_dr_step_kernel (ZB_M_EVENTS 1, ZB_M_BI 1): the events build with the base composite
-// body's mass properties per env (include/zbot_base_inertia.h; one more argument, the side buffer
-// float4[N][4]: the body's three table rows, then the base link's COM in the body frame).
-// A fourth stamp, zb_m_terms_step_kernel (ZB_M_EVENTS 1, ZB_M_BI 1, ZB_M_TERMS 1): the dr build with the five
-// reward terms of include/zbot_manager_terms.h (two more arguments, both pointers: the configuration's
-// device copy, read in the reward epilogue only, and the term-state side buffer float[ZB_MT_STATE_DIM][N],
-// whose rows ride in the LDS carry behind the event state). The feet's contact timers ride in the air
-// timers' registers through the substep loop (a foot is in one mode at a time: > 0 air time, < 0 minus the
-// contact time); everything else is in the reward epilogue. What the build costs in registers and
-// scratch: profiles/manager_terms/kernel_resources.txt, held by tests/test_manager_terms_resources.py
-// (40 / 56 B at two waves per SIMD against the dr build's 40 / 52 B, none at one; the TGS two-wave build
-// parks a third per-lane 64-bit detection mask in scratch and reloads it inside a detection loop, one
-// in-loop reload more than the dr build; DESIGN.md §9).
+// The manager step kernel's text. sim_manager.h stamps it four times; every stamp #defines the eight
+// parameters checked below immediately before its #include, and this file #undefs them at its end, so no
+// stamp inherits from another. One text, so the stamps cannot drift; separate kernels, because a shared
+// __device__ body does not reproduce the events-off code (profiles/manager_events/kernel_resources.txt).
+//
+//   kernel                    EVENTS BI TERMS  arguments after seed (ZB_M_EV_PARAMS), before wc
+//   zb_m_step_kernel            0    0    0    none: the kernel as it was before the events existed
+//   zb_m_events_step_kernel     1    0    0    evc, evst
+//   zb_m_dr_step_kernel         1    1    0    evc, evst, bi
+//   zb_m_terms_step_kernel      1    1    1    evc, evst, bi, tmc, tmst
+//
+// ZB_M_EVENTS: the interval push and the yaw / heading commands of include/zbot_manager_events.h (evc the
+// configuration, evst the event-state side buffer; ZB_M_EV_INIT builds the MEv record from them).
+// ZB_M_BI: the base composite body's mass properties per env, include/zbot_base_inertia.h (bi, named by
+// ZB_M_BI_ROWS: the side buffer float4[N][4], the body's three table rows, then the base link's COM in the
+// body frame).
+// ZB_M_TERMS: the five reward terms of include/zbot_manager_terms.h (tmc the configuration's device copy,
+// read in the reward epilogue only; tmst the term-state side buffer float[ZB_MT_STATE_DIM][N], whose rows
+// ride in the LDS carry behind the event state; ZB_M_TERMS_INIT builds the MTerms record). The feet's
+// contact timers ride in the air timers' registers through the substep loop (a foot is in one mode at a
+// time: > 0 air time, < 0 minus the contact time); everything else is in the reward epilogue. What the
+// build costs in registers and scratch: profiles/manager_terms/kernel_resources.txt, held by
+// tests/test_manager_terms_resources.py (40 / 56 B at two waves per SIMD against the dr build's 40 / 52 B,
+// none at one; the TGS two-wave build parks a third per-lane 64-bit detection mask in scratch and reloads
+// it inside a detection loop, one in-loop reload more than the dr build; DESIGN.md §9).
+#if !defined(ZB_M_STEP_KERNEL) || !defined(ZB_M_EVENTS) || !defined(ZB_M_EV_PARAMS) || !defined(ZB_M_EV_INIT) || \
+    !defined(ZB_M_BI) || !defined(ZB_M_BI_ROWS) || !defined(ZB_M_TERMS) || !defined(ZB_M_TERMS_INIT)
+#error "zbot_m_step.inc: a stamp must define all eight ZB_M_* parameters (see the stamps in sim_manager.h)"
+#endif
 template <bool kTgs, int kOcc>
 __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
     const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg, int N, float* __restrict__ st,
@@ -478,3 +488,11 @@ __global__ __launch_bounds__(WGT, kOcc) void ZB_M_STEP_KERNEL(
   if constexpr (kTerms) m_terms_store(q, xcd_block(blockIdx.x, gridDim.x) * EPW, N, tm.st);
   step_finish<ZB_M_LINK_MU, ZB_M_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
 }
+#undef ZB_M_STEP_KERNEL
+#undef ZB_M_EVENTS
+#undef ZB_M_EV_PARAMS
+#undef ZB_M_EV_INIT
+#undef ZB_M_BI
+#undef ZB_M_BI_ROWS
+#undef ZB_M_TERMS
+#undef ZB_M_TERMS_INIT
