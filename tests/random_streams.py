@@ -2,7 +2,7 @@
 the law checks on them: shared by the CPU oracle tests (tests/test_random_laws.py) and the device
 tests (tests/test_gpu_random_streams.py), which run the same scenarios through two backends.
 
-Draw-index map (``draw(env_hash(seed, ctr, env), k)``; zbot_sim.hip and oracle/zbot_oracle.c):
+Draw-index map (``draw(env_hash(seed, ctr, env), k)``; csrc/sim_standup.h and oracle/zbot_oracle.c):
 reset pose 1..4 (x, y, roll, yaw); reset command 5..7 (v4: sign, velocity, yaw; manager: lin x,
 lin y, standing); v4 command interval 8; interval command 9..11; manager observation noise 16..31;
 the full-reset episode length is ``env_hash % max_episode_length`` itself.

@@ -1,7 +1,7 @@
 """zbot_lab_amd — MI355X-native batched simulator for the ZBOT-6 ``zbot-6b-walking-v2`` task.
 
 Hot path: one fused HIP kernel per policy step (``csrc/zbot_sim.hip``, one translation unit with
-``csrc/sim_manager.h`` and ``csrc/zbot_m_step.inc`` -> ``libzbot.so``, C ABI in ``include/zbot.h``).
+the ``csrc/sim_*.h`` pieces and ``csrc/zbot_m_step.inc`` -> ``libzbot.so``, C ABI in ``include/zbot.h``).
 Host side mirrors the reference's DirectRLEnv / rsl_rl VecEnv interfaces.
 """
 import os as _os

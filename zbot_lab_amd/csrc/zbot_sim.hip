@@ -20,10 +20,11 @@
 // The algorithm is the one restated on the CPU in oracle/zbot_oracle.c (the parity oracle);
 // the two are written independently and compared by tests/test_gpu_parity.py.
 //
-// One translation unit, and this file is the only one given to the compiler. The manager-based env (its
-// events, reward terms and per-env base inertia, and the four stamps of zbot_m_step.inc) lives in
-// sim_manager.h, included below at its old place between walking v4 and the critic observations; the
-// rest of the text is still here, under its banners.
+// One translation unit, and this file is the only one given to the compiler. The three later tasks live in
+// pieces beside it, included below at their old places between walking v2's kernels and the critic
+// observations: sim_standup.h (zbot-6b-standup-v0), sim_walking_v4.h (zbot-6b-walking-v4) and sim_manager.h
+// (the manager-based env: its events, reward terms and per-env base inertia, and the four stamps of
+// zbot_m_step.inc). The rest of the text is still here, under its banners.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -3752,773 +3753,8 @@ __global__ __launch_bounds__(WGT, ZB_WAVES_PER_SIMD) void zb_substeps_kernel(con
 }
 
 
-// =========================================================================== stand-up task
-// zbot-6b-standup-v0 (reference zbot_direct_6_standup_env_v0.py = standup.py) on the same robot
-// and physics: ZBOT_6S_CFG_2 lying init (zbot_cfg.py:721-763), per-link friction from the
-// startup material randomisation, rewards from the post-step link states, died on a height drop,
-// reset pose randomised in-kernel (reset_root_state_uniform) and a device-side curriculum.
-
-__host__ __device__ __forceinline__ float u01(uint64_t h) { return (float)(h >> 40) * (1.0f / 16777216.0f); }
-
-// reward weight of term t in curriculum stage `stage` (compile-time indices into the kernarg table)
-__device__ __forceinline__ float stage_weight(const zb_task_cfg& cfg, int stage, int t) {
-  float w = cfg.stage_scales[0][t];
-#pragma unroll
-  for (int sg = 1; sg < ZB_MAX_STAGES; ++sg) w = stage == sg ? cfg.stage_scales[sg][t] : w;
-  return w;
-}
-
-// counter-based random stream of env i at call ctr; draw k of it (shared with the oracle)
-__device__ __forceinline__ uint64_t env_hash(uint64_t seed, uint64_t ctr, int i) {
-  return hash64(seed ^ hash64(ctr * 0x100000001B3ull + (uint64_t)i));
-}
-__device__ __forceinline__ float draw(uint64_t h, int k) { return u01(hash64(h + 0x632BE59BD9B4E019ull * (uint64_t)k)); }
-
-// reset_root_state_uniform (standup.py:33-97, v4.py:59-105) from stream h (draws 1..4): x, y,
-// roll, yaw ~ U (the cfg ranges; pitch / z / velocities 0), root = default + (x, y, 0), quat =
-// quat_from_euler_xyz(roll, 0, yaw) applied in the world frame (delta * default, standup) or the
-// body frame (default * delta, v4), normalised; joints default, every velocity zero. Returns the
-// yaw sample (the events store it as env.current_yaw).
-__device__ __forceinline__ float reset_pose(MP m, const zb_task_cfg& cfg, uint64_t h, Phys& p) {
-  float r[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    r[k] = draw(h, k + 1) * (cfg.reset_pose_range[k][1] - cfg.reset_pose_range[k][0]) + cfg.reset_pose_range[k][0];
-  float sr, cr, sy, cy;
-  sincos_r(0.5f * r[2], &sr, &cr);
-  sincos_r(0.5f * r[3], &sy, &cy);
-  const float dq[4] = {cy * cr, cy * sr, sy * sr, sy * cr};  // quat_from_euler_xyz(roll, 0, yaw)
-  // the sampled pose is the Isaac Lab root's (the chain root unless the asset is rooted elsewhere):
-  // its default pose is chain-root default * T (T = api_root_in_root, identity for the others)
-  const float q0[4] = {m->default_root_quat[0], m->default_root_quat[1], m->default_root_quat[2],
-                       m->default_root_quat[3]};
-  const float tT[3] = {m->api_root_in_root[0], m->api_root_in_root[1], m->api_root_in_root[2]};
-  const float qT[4] = {m->api_root_in_root[3], m->api_root_in_root[4], m->api_root_in_root[5], m->api_root_in_root[6]};
-  float qa0[4], ta[3];
-  qmul(q0, qT, qa0);
-  qrot(q0, tT, ta);
-  float qa[4];
-  if (cfg.reset_pose_body_frame) qmul(qa0, dq, qa);
-  else qmul(dq, qa0, qa);
-  qnormalize(qa);
-  const float pa[3] = {m->default_root_pos[0] + ta[0] + r[0], m->default_root_pos[1] + ta[1] + r[1],
-                       m->default_root_pos[2] + ta[2]};
-  // back to the chain root: q = qa * conj(qT), p = pa - R(q) tT
-  const float qTc[4] = {qT[0], -qT[1], -qT[2], -qT[3]};
-  float qn[4], tq[3];
-  qmul(qa, qTc, qn);
-  qrot(qn, tT, tq);
-#pragma unroll
-  for (int a = 0; a < 4; ++a) p.quat[a] = qn[a];
-  p.pos[0] = pa[0] - tq[0];
-  p.pos[1] = pa[1] - tq[1];
-  p.pos[2] = pa[2] - tq[2];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { p.lv[a] = 0.f; p.av[a] = 0.f; }
-#pragma unroll
-  for (int j = 0; j < ND; ++j) { p.jq[j] = m->default_joint_pos[j]; p.jqd[j] = 0.f; }
-  return r[3];
-}
-
-__device__ __forceinline__ void su_reset_pose(MP m, const zb_task_cfg& cfg, uint64_t seed, uint64_t ctr, int i,
-                                              Phys& p) {
-  (void)reset_pose(m, cfg, env_hash(seed, ctr, i), p);
-}
-
-// One stand-up policy step per team (same mapping as zb_step_kernel; no contact sensor).
-template <bool kTgs, int kOcc, bool kRefresh = false, bool kRf = false>
-__global__ __launch_bounds__(WGT, kOcc) void zb_su_step_kernel(
-    const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg, int N, float* __restrict__ st,
-    const float* __restrict__ act, float* __restrict__ obs, float* __restrict__ rew, uint8_t* __restrict__ term,
-    uint8_t* __restrict__ trunc, int64_t* __restrict__ done, float* __restrict__ acc,
-    const Counters* __restrict__ cnt, uint64_t seed, float* __restrict__ wc) {
-  MP m = to_mp(mg);
-  __shared__ float4 lds[LDS4];
-  if (kOcc == 1) asm volatile("" ::: "a255");  // (zb_step_kernel: kOcc)
-  const int lane = threadIdx.x;
-  const int env = xcd_block(blockIdx.x, gridDim.x) * EPW + lane / TL;
-  const int i = env < N ? env : N - 1;
-  const bool lead = env < N && lane % TL == 0;
-  const Q q = make_q(lds, lane, links);
-  for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
-  Stamps sp;
-  sp.begin();
-  Phys p;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) p.quat[a] = ST(ZB_S_ROOT_QUAT + a);
-#pragma unroll
-  for (int j = 0; j < ND; ++j) { p.jq[j] = ST(ZB_S_JOINT_POS + j); p.jqd[j] = ST(ZB_S_JOINT_VEL + j); }
-  if (q.s < NL) {  // lane l: link l (visible after the first barrier)
-    q.fric(q.s) = ST(ZB_SU_LINK_MU + q.s);
-    q.fricd(q.s) = ST(ZB_SU_LINK_MU_D + q.s);
-  }
-
-  // _pre_physics_step (standup.py:538-551, mode 1)
-  const bool writer = q.s == 0;
-  const float step_dt = cfg.sim_dt * (float)cfg.decimation;
-  float target[ND];
-  {
-    Pre pr;
-    pre_action<ZB_SU_P_DELTA, ZB_SU_ACTIONS, false>(m, cfg, st, N, i, act, q.s, step_dt, pr, target);
-    if (writer) q.pre() = pr;
-  }
-
-  SensorOut so;
-  wc_load(q, wc, N, i);  // the first substep's GJK warm start
-  sp.mark(0);
-  for (int k = 0; k < cfg.decimation; ++k) {
-    substep<false, true, kTgs, kRefresh, kRf>(m, cfg, p, target, q, false, true, so, nullptr, nullptr, sp);
-    sp.mark(7);
-  }
-  Pre pr;
-  const float wc_row = after_substeps(m, q, st, pr);
-  const float czl0 = ST(ZB_SU_CENTER_Z_LAST);
-  const float ep_len = ST(ZB_SU_EP_LEN) + 1.f;
-  float sums0[ZB_SU_NUM_REWARD_TERMS];
-#pragma unroll
-  for (int t = 0; t < ZB_SU_NUM_REWARD_TERMS; ++t) sums0[t] = ST(ZB_SU_EP_SUMS + t);
-  const int stage = cnt->stage;
-
-  // post-step link states (_compute_intermediate_values 571-591, body_link_state_w)
-  float z4, z6, z8, vz5, vz6, fz[2][3], obs_q[4];
-  {
-    wave_sync();
-    fk_team_pose(p, q);
-    wave_sync();
-    float S[ND][6], org[ND][3];
-    read_joints(q, S, org);
-    float lp[3], lq[4], v[3], R[9];
-    link_pose_q(m, q, 4, lp, lq);
-    z4 = lp[2] + p.pos[2];
-    link_pose_q(m, q, 8, lp, lq);
-    z8 = lp[2] + p.pos[2];
-    link_pose_q(m, q, 6, lp, obs_q);
-    z6 = lp[2] + p.pos[2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      link_pose_q(m, q, f == 0 ? 0 : 11, lp, lq);
-      qmat(lq, R);
-      const float sg = f == 0 ? 1.f : -1.f;  // axis_z_feet = (0,0,1), (0,0,-1) (standup.py:503-505)
-      fz[f][0] = sg * R[2]; fz[f][1] = sg * R[5]; fz[f][2] = sg * R[8];
-    }
-    link_origin_vel_q(m, q, p, S, 6, v);
-    vz6 = v[2];
-    link_origin_vel_q(m, q, p, S, 5, v);
-    vz5 = v[2];
-  }
-
-  // _get_dones (standup.py:634-643)
-  const bool time_out = ep_len >= (float)(cfg.max_episode_length - 1);
-  const bool blowup = phys_bad(p);  // non-finite guard (phys_bad)
-  const bool died = (czl0 - z6) > cfg.center_z_drop || blowup;
-  const float czl = ((int)ep_len % cfg.center_z_period == cfg.center_z_period - 1) ? z6 : czl0;
-
-  // _get_rewards (standup.py:620-632): reward_func() * scale * step_dt per term, dict order
-  float r[ZB_SU_NUM_REWARD_TERMS];
-  {
-    const float rh = z6 + 0.5f * z4 + 0.5f * z8 - 0.1f;  // _reward_upward_2 (843-856)
-    float up = z6 < 0.22f ? rh + 0.5f * vz6 + 0.5f * vz5 : 1.35f;
-    if ((fz[0][2] < 0.5f || fz[1][2] < 0.5f) && z6 > 0.1f) up = -5.f * up;
-    r[ZB_SU_R_UPWARD_2] = up;
-  }
-  r[ZB_SU_R_SHAPE_SYMMETRY] = fabsf(pr.pdel[0] + pr.pdel[5]) + fabsf(pr.pdel[1] + pr.pdel[4]) +
-                              fabsf(pr.pdel[2] + pr.pdel[3]);  // 782-789
-  {
-    float sd = 0.f;
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const float d[3] = {fz[f][0], fz[f][1], fz[f][2] - 1.f};
-      sd += sqrtf(dot3(d, d));
-    }
-    r[ZB_SU_R_FEET_DOWNWARD] = sd;  // 735-745
-  }
-  r[ZB_SU_R_FEET_DOWNWARD_4] = z6 < 0.15f ? fz[0][2] + fz[1][2] : 1.6f;  // 827-840
-  float w[ZB_SU_NUM_REWARD_TERMS];
-#pragma unroll
-  for (int t = 0; t < ZB_SU_NUM_REWARD_TERMS; ++t) w[t] = stage_weight(cfg, stage, t);
-  float reward = 0.f, sums[ZB_SU_NUM_REWARD_TERMS];
-#pragma unroll
-  for (int t = 0; t < ZB_SU_NUM_REWARD_TERMS; ++t) {
-    const float v = (r[t] * w[t]) * step_dt;
-    reward += v;
-    sums[t] = sums0[t] + v;
-  }
-  if (died) reward -= cfg.terminal_penalty;  // 629-630
-  if (blowup) {
-    reward = -cfg.terminal_penalty;
-#pragma unroll
-    for (int t = 0; t < ZB_SU_NUM_REWARD_TERMS; ++t) sums[t] = sums0[t];
-  }
-  const bool reset = died || time_out;
-
-  // _reset_idx (645-703): episode log (sums per second of the env's own episode), new random
-  // root pose, default joints; the reset env's observation sees the new pose
-  const uint64_t lmask = __ballot(reset && lead);
-  if (reset) {
-    if (lead) {
-      const float dur = fmaxf(ep_len * step_dt, step_dt);
-      float* lr = log_row(q);
-#pragma unroll
-      for (int t = 0; t < ZB_SU_NUM_REWARD_TERMS; ++t) lr[t] = sums[t] / dur;
-      lr[ACC_NRES] = 1.f;
-      lr[ACC_DIED] = died ? 1.f : 0.f;
-      lr[ACC_TOUT] = time_out ? 1.f : 0.f;
-    }
-    su_reset_pose(m, cfg, seed, cnt->calls, i, p);
-    const float4 qr = q.dflt()[3];
-    const float qrel[4] = {qr.x, qr.y, qr.z, qr.w};
-    qmul(p.quat, qrel, obs_q);
-  }
-  log_flush(q, lmask, acc);
-  store_wc_row(q, wc, N, i, reset, wc_row);
-  sp.mark(12);
-  if (writer) {
-    const Live live{reset};
-    stage_phys(q, p);
-#pragma unroll
-    for (int j = 0; j < ND; ++j) { OUT(ZB_SU_P_DELTA + j) = live(pr.pdel[j]); OUT(ZB_SU_ACTIONS + j) = live(pr.a_now[j]); }
-    OUT(ZB_SU_CENTER_Z_LAST) = reset ? cfg.center_z_init : czl;
-    OUT(ZB_SU_EP_LEN) = live(ep_len);
-#pragma unroll
-    for (int t = 0; t < ZB_SU_NUM_REWARD_TERMS; ++t) OUT(ZB_SU_EP_SUMS + t) = live(sums[t]);
-
-    // _get_observations (593-618): base quat, joint_pos - default, joint_vel, actions
-    float* o = &q.stg(ZB_SU_LINK_MU);
-    o[0] = obs_q[0]; o[1] = obs_q[1]; o[2] = obs_q[2]; o[3] = obs_q[3];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      o[4 + j] = p.jq[j] - m->default_joint_pos[j];
-      o[10 + j] = p.jqd[j];
-      o[16 + j] = live(pr.a_now[j]);
-    }
-    stage_result<ZB_SU_LINK_MU, ZB_SU_OBS_DIM>(q, reward, died, time_out);
-  }
-  step_finish<ZB_SU_LINK_MU, ZB_SU_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
-}
-
-// explicit resets (env_ids, or all when ids == nullptr): episode log into acc, then the reset
-// pose of su_reset_pose; one thread per env
-__global__ void zb_su_reset_kernel(const zb_model* __restrict__ mg, zb_task_cfg cfg, int N, float* __restrict__ st,
-                                   const int32_t* __restrict__ ids, int n, float* __restrict__ acc,
-                                   const Counters* __restrict__ cnt, uint64_t seed) {
-  MP m = to_mp(mg);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int i = ids ? ids[t] : t;
-  if (i < 0 || i >= N) return;
-  const float step_dt = cfg.sim_dt * (float)cfg.decimation;
-  const float dur = fmaxf(ST(ZB_SU_EP_LEN) * step_dt, step_dt);
-#pragma unroll
-  for (int k = 0; k < ZB_SU_NUM_REWARD_TERMS; ++k) atomicAdd(&acc_slot(acc, t)[k], ST(ZB_SU_EP_SUMS + k) / dur);
-  atomicAdd(&acc_slot(acc, t)[ACC_NRES], 1.f);
-  Phys p;
-  su_reset_pose(m, cfg, seed, cnt->calls, i, p);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { ST(ZB_S_ROOT_POS + a) = p.pos[a]; ST(ZB_S_ROOT_LINVEL + a) = p.lv[a]; ST(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) ST(ZB_S_ROOT_QUAT + a) = p.quat[a];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) {
-    ST(ZB_S_JOINT_POS + j) = p.jq[j]; ST(ZB_S_JOINT_VEL + j) = p.jqd[j];
-    ST(ZB_SU_P_DELTA + j) = 0.f; ST(ZB_SU_ACTIONS + j) = 0.f;
-  }
-  ST(ZB_SU_CENTER_Z_LAST) = cfg.center_z_init;
-  ST(ZB_SU_EP_LEN) = 0.f;
-#pragma unroll
-  for (int k = 0; k < ZB_SU_NUM_REWARD_TERMS; ++k) ST(ZB_SU_EP_SUMS + k) = 0.f;
-}
-
-// the observation of env i's current state (standup.py:593-618) into the row o (out of line: obs_row)
-__device__ __noinline__ void su_obs_row(const zb_model* mg, int N, const float* st, int i, float* o) {
-  MP m = to_mp(mg);
-  Phys p;
-  load_phys(st, N, i, p);
-  Kin k;
-  fk(m, p, k);
-  float bp[3], bq[4];
-  link_pose(m, k, 6, bp, bq);
-  o[0] = bq[0]; o[1] = bq[1]; o[2] = bq[2]; o[3] = bq[3];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) {
-    o[4 + j] = p.jq[j] - m->default_joint_pos[j];
-    o[10 + j] = p.jqd[j];
-    o[16 + j] = st[(size_t)(ZB_SU_ACTIONS + j) * N + i];
-  }
-}
-
-__global__ void zb_su_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
-                                     float* __restrict__ obs) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  su_obs_row(mg, N, st, i, obs + (size_t)i * ZB_SU_OBS_DIM);
-}
-
-// per-link friction [N][NL] -> state rows ZB_SU_LINK_MU (mu == nullptr: fill with `fill`)
-__global__ void zb_su_friction_kernel(int N, float* __restrict__ st, const float* __restrict__ mu, float fill, int row) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= N * NL) return;
-  const int i = t / NL, l = t % NL;
-  st[(size_t)(row + l) * N + i] = mu ? mu[t] : fill;
-}
-
-// =========================================================================== walking v4
-// zbot-6b-walking-v4 (reference zbot_direct_6dof_bipedal_env_v4.py = v4.py): v2's robot and
-// physics with forward-velocity / heading commands (reset and interval resample events), a
-// history-3 contact sensor that also tracks contact time, 15 reward terms evaluated on the
-// post-step state, and the two curricula (stage weights + command ranges in the device counters).
-
-__device__ __forceinline__ float wrap_to_pi(float x) {  // isaaclab.utils.math.wrap_to_pi
-  float a = fmodf(x, TWO_PI_F);
-  if (a < 0.f) a += TWO_PI_F;
-  return a > PI_F ? a - TWO_PI_F : a;
-}
-
-// resample_commands (v4.py:107-135) from stream h, draws k0 .. k0+2, with the device-side params
-__device__ __forceinline__ void v4_resample(const zb_task_cfg& cfg, const Counters* cnt, uint64_t h, int k0,
-                                            float cur_yaw, float cmd[2], float& target) {
-  const float lo = cnt->vel[0], hi0 = cnt->vel[1];
-  if (cfg.cmd_dual_sign) {
-    const float sg = draw(h, k0) < cnt->prob_pos ? 1.f : -1.f;  // bernoulli(prob_pos) * 2 - 1
-    const float hi = hi0 + cfg.cmd_offset * (sg - 1.f);
-    cmd[0] = (draw(h, k0 + 1) * (hi - lo) + lo) * sg;
-  } else {
-    cmd[0] = draw(h, k0 + 1) * (hi0 - lo) + lo;
-  }
-  cmd[1] = draw(h, k0 + 2) * (cnt->yaw[1] - cnt->yaw[0]) + cnt->yaw[0];
-  target = wrap_to_pi(cur_yaw + cmd[1]);
-}
-
-// prologue values parked in LDS across the physics (overlays the Pre record)
-struct PreV4 {
-  float a_now[ND], pdel[ND], jqd_prev[ND], action_rate;
-};
-static_assert(sizeof(PreV4) <= 16 * PRE4, "PreV4 fits PRE4 granules");
-
-template <bool kTgs, int kOcc>
-__global__ __launch_bounds__(WGT, kOcc) void zb_v4_step_kernel(
-    const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg, int N, float* __restrict__ st,
-    const float* __restrict__ act, float* __restrict__ obs, float* __restrict__ rew, uint8_t* __restrict__ term,
-    uint8_t* __restrict__ trunc, int64_t* __restrict__ done, float* __restrict__ acc,
-    const Counters* __restrict__ cnt, uint64_t seed, float* __restrict__ wc) {
-  MP m = to_mp(mg);
-  __shared__ float4 lds[LDS4];
-  if (kOcc == 1) asm volatile("" ::: "a255");  // (zb_step_kernel: kOcc)
-  const int lane = threadIdx.x;
-  const int env = xcd_block(blockIdx.x, gridDim.x) * EPW + lane / TL;
-  const int i = env < N ? env : N - 1;
-  const bool lead = env < N && lane % TL == 0;
-  const Q q = make_q(lds, lane, links);
-  for (int t = LNK_G + lane; t < LNK4; t += WGT) lds[LNK_OFF + t] = links[t];
-  Stamps sp;
-  sp.begin();
-  Phys p;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { p.pos[a] = ST(ZB_S_ROOT_POS + a); p.lv[a] = ST(ZB_S_ROOT_LINVEL + a); p.av[a] = ST(ZB_S_ROOT_ANGVEL + a); }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) p.quat[a] = ST(ZB_S_ROOT_QUAT + a);
-#pragma unroll
-  for (int j = 0; j < ND; ++j) { p.jq[j] = ST(ZB_S_JOINT_POS + j); p.jqd[j] = ST(ZB_S_JOINT_VEL + j); }
-  const float* cst = carry_prefetch<ZB_V4_STATE_DIM>(q, st, N, i);
-
-  // _pre_physics_step (v4.py:776-804, mode 1)
-  const bool writer = q.s == 0;
-  const float step_dt = cfg.sim_dt * (float)cfg.decimation;
-  PreV4& pv = *reinterpret_cast<PreV4*>(&q.pre());
-  float target[ND];
-  {
-    PreV4 pr;
-    pr.action_rate = 0.f;
-    float a_tanh[ND];
-    actions_tanh(act, i, q.s, a_tanh);
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      const float a_prev = ST(ZB_V4_ACTIONS + j);
-      pr.a_now[j] = a_tanh[j];
-      pr.pdel[j] = clampf(ST(ZB_V4_P_DELTA + j) + PI_F * pr.a_now[j] * cfg.joint_speed_limit * step_dt, -PI_F, PI_F);
-      target[j] = pr.pdel[j] + m->default_joint_pos[j];
-      pr.action_rate += (pr.a_now[j] - a_prev) * (pr.a_now[j] - a_prev);
-      pr.jqd_prev[j] = 0.f;
-    }
-    if (writer) pv = pr;
-  }
-
-  // 4 substeps, each followed by the contact sensor's update (record parked in LDS); the last one's
-  // applied torques feed the torques term, the joint velocities before it give Isaac Lab's
-  // finite-difference joint_acc (ArticulationData.update every substep)
-  SensorOut so;
-  wc_load(q, wc, N, i);  // the first substep's GJK warm start
-  sp.mark(0);
-  for (int k = 0; k < cfg.decimation; ++k) {
-    const bool last = k == cfg.decimation - 1;
-    if (last && writer) {
-#pragma unroll
-      for (int j = 0; j < ND; ++j) pv.jqd_prev[j] = p.jqd[j];
-    }
-    substep<false, false, kTgs>(m, cfg, p, target, q, true, true, so, nullptr, nullptr, sp);
-    sens_record(q, k, so);
-    sp.mark(7);
-  }
-  PreV4 pr;
-  const float wc_row = after_substeps(m, q, st, pr);
-
-  // ContactSensor (history 3, updated every physics step; air / contact timers incl.
-  // last_contact_time)
-  float fz_sum[2], fm_max;
-  float air_cur[2], con_cur[2], air_last[2], con_last[2], feetF[2];
-  bool in_contact[2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    air_cur[f] = CST(ZB_V4_FEET_AIR_CUR + f);
-    con_cur[f] = CST(ZB_V4_FEET_CONTACT_CUR + f);
-    air_last[f] = CST(ZB_V4_FEET_AIR_LAST + f);
-    con_last[f] = CST(ZB_V4_FEET_CONTACT_LAST + f);
-  }
-  sens_replay<ZB_V4_HIST>(q, cst, 1, 0, ZB_V4_FEET_FZ_HIST, ZB_V4_UNDES_FMAX_HIST, cfg.decimation, cfg.sim_dt,
-                          cfg.contact_force_threshold, fz_sum, fm_max, air_cur, air_last, con_cur, con_last);
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    in_contact[f] = con_cur[f] > 0.f;
-    feetF[f] = fz_sum[f] / (float)ZB_V4_HIST;  // mean over the history (v4.py:846-849)
-  }
-  const float ep_len = CST(ZB_V4_EP_LEN) + 1.f;
-  float cmd[2] = {CST(ZB_V4_COMMANDS), CST(ZB_V4_COMMANDS + 1)};
-  float tgt = CST(ZB_V4_TARGET_YAW);
-  float ileft = CST(ZB_V4_INTERVAL_LEFT);
-  float f_last[2] = {CST(ZB_V4_FEET_F_LAST), CST(ZB_V4_FEET_F_LAST + 1)};
-  float step_len[2] = {CST(ZB_V4_FEET_STEP_LEN), CST(ZB_V4_FEET_STEP_LEN + 1)};
-  float down[2][3];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) down[f][a] = CST(ZB_V4_FEET_DOWN_POS + 3 * f + a);
-  float sums0[ZB_V4_NUM_REWARD_TERMS];
-#pragma unroll
-  for (int t = 0; t < ZB_V4_NUM_REWARD_TERMS; ++t) sums0[t] = CST(ZB_V4_EP_SUMS + t);
-  const int stage = cnt->stage;
-
-  // _compute_intermediate_values (v4.py:809-849) on the post-step state
-  float bq[4], sh[3], fwd[3], vb[3], feet[2][3], fzax[2][3], fxax[2][3], fvel[2][3];
-  bool died;
-  {
-    wave_sync();
-    fk_team_pose(p, q);
-    wave_sync();
-    float S[ND][6], org[ND][3];
-    read_joints(q, S, org);
-    float bp[3], R[9], fq[4];
-    link_pose_q(m, q, 6, bp, bq);
-    qmat(bq, R);
-    sh[0] = R[2]; sh[1] = R[5]; sh[2] = R[8];            // quat_apply(base_quat, z)
-    fwd[0] = sh[1]; fwd[1] = -sh[0]; fwd[2] = 0.f;       // GRAVITY_VEC_W x shoulder
-    link_origin_vel_q(m, q, p, S, 6, vb);                // body_link_lin_vel_w[base]
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const int l = f == 0 ? 0 : 11;
-      link_pose_q(m, q, l, feet[f], fq);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) feet[f][a] += p.pos[a];
-      qmat(fq, R);
-      const float sg = f == 0 ? 1.f : -1.f;
-      fzax[f][0] = sg * R[2]; fzax[f][1] = sg * R[5]; fzax[f][2] = sg * R[8];
-      fxax[f][0] = R[0]; fxax[f][1] = R[3]; fxax[f][2] = R[6];
-      link_com_vel_q(m, q, p, S, l, fvel[f]);            // body_com_lin_vel_w[feet]
-    }
-    const float base_z = bp[2] + p.pos[2];
-    // _get_dones (v4.py:896-918)
-    const float fm = fm_max;
-    died = fm > cfg.undesired_force_threshold || base_z < cfg.termination_height;
-  }
-  const bool time_out = ep_len >= (float)(cfg.max_episode_length - 1);
-  const bool blowup = phys_bad(p);  // non-finite guard (phys_bad), as in the walking kernel
-  died |= blowup;
-  float cur_yaw = atan2f(fwd[1], fwd[0]);
-  float he;
-  {
-    float sn, cs;
-    sincos_r(tgt - cur_yaw, &sn, &cs);
-    he = atan2f(sn, cs);
-  }
-  const float vfwd = dot3(vb, fwd);
-
-  // _get_rewards (v4.py:883-894), terms 1003-1171 in dict order
-  float r[ZB_V4_NUM_REWARD_TERMS];
-  {
-    const float e = cmd[0] - vfwd;
-    r[ZB_V4_R_TRACK_LIN_VEL_X] = __expf(-e * e / 0.25f);
-    r[ZB_V4_R_TRACK_HEADING_YAW] = __expf(-he * he / 0.25f);
-    const float vy = dot3(vb, sh);
-    r[ZB_V4_R_LIN_VEL_Y] = vy * vy;
-    r[ZB_V4_R_ACTION_RATE] = pr.action_rate;
-    r[ZB_V4_R_TORQUES] = so.tau2;
-    float jv = 0.f, ja = 0.f;
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      jv += p.jqd[j] * p.jqd[j];
-      const float aj = (p.jqd[j] - pr.jqd_prev[j]) / cfg.sim_dt;
-      ja += aj * aj;
-    }
-    r[ZB_V4_R_JOINT_VEL] = jv;
-    r[ZB_V4_R_JOINT_ACC] = ja;
-    float sd = 0.f, sfw = 0.f;
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const float dz[3] = {fzax[f][0], fzax[f][1], fzax[f][2] - 1.f};
-      sd += sqrtf(dot3(dz, dz));
-      const float dx[3] = {fxax[f][0] - fwd[0], fxax[f][1] - fwd[1], fxax[f][2] - fwd[2]};
-      sfw += sqrtf(dot3(dx, dx));
-    }
-    r[ZB_V4_R_FEET_DOWNWARD] = sd;
-    r[ZB_V4_R_FEET_FORWARD] = sfw;
-    // step_length (v4.py:1058-1095): touchdown foot records its step along the heading, signed by
-    // the commanded direction; the stored lengths decay by 0.99 per step
-    const float csg = cmd[0] > 0.f ? 1.f : (cmd[0] < 0.f ? -1.f : 0.f);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      if (feetF[f] > 10.f && f_last[f] < 10.f) {
-        const float dv[3] = {feet[f][0] - down[f][0], feet[f][1] - down[f][1], feet[f][2] - down[f][2]};
-        step_len[f] = dot3(dv, fwd) * csg;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) down[f][a] = feet[f][a];
-      }
-    }
-    const float mn = fminf(step_len[0], step_len[1]);
-    step_len[0] *= 0.99f;
-    step_len[1] *= 0.99f;
-    f_last[0] = feetF[0];
-    f_last[1] = feetF[1];
-    r[ZB_V4_R_STEP_LENGTH] = tanh_r(15.f * mn);
-    // feet_air_time_biped (1129-1143)
-    const bool single = (in_contact[0] ? 1 : 0) + (in_contact[1] ? 1 : 0) == 1;
-    float bi = 3.4e38f;
-#pragma unroll
-    for (int f = 0; f < 2; ++f) bi = fminf(bi, single ? (in_contact[f] ? con_cur[f] : air_cur[f]) : 0.f);
-    r[ZB_V4_R_FEET_AIR_TIME_BIPED] = fminf(bi, 2.f);
-    // airtime_variance (1097-1103): unbiased variance of two values = (a - b)^2 / 2
-    const float da = fminf(air_last[0], 0.5f) - fminf(air_last[1], 0.5f);
-    const float dc = fminf(con_last[0], 0.5f) - fminf(con_last[1], 0.5f);
-    r[ZB_V4_R_AIRTIME_VARIANCE] = 0.5f * da * da + 0.5f * dc * dc;
-    float sl = 0.f;
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-      sl += sqrtf(fvel[f][0] * fvel[f][0] + fvel[f][1] * fvel[f][1]) * (feetF[f] > 1.f ? 1.f : 0.f);
-    r[ZB_V4_R_FEET_SLIDE] = sl;
-    r[ZB_V4_R_FEET_HARMONY] = (air_last[0] + air_last[1]) - 3.f * fabsf(air_last[0] - air_last[1]);
-    const float dx = feet[0][0] - feet[1][0], dy = feet[0][1] - feet[1][1];
-    r[ZB_V4_R_FEET_CLOSE] = fmaxf(0.115f - sqrtf(dx * dx + dy * dy), 0.f);
-  }
-  float reward = 0.f, sums[ZB_V4_NUM_REWARD_TERMS];
-#pragma unroll
-  for (int t = 0; t < ZB_V4_NUM_REWARD_TERMS; ++t) {
-    const float v = (r[t] * stage_weight(cfg, stage, t)) * step_dt;
-    reward += v;
-    sums[t] = sums0[t] + v;
-  }
-  if (died) reward -= cfg.terminal_penalty;  // v4.py:892-893
-  if (blowup) {  // finite reward, the episode sums without this step
-    reward = -cfg.terminal_penalty;
-#pragma unroll
-    for (int t = 0; t < ZB_V4_NUM_REWARD_TERMS; ++t) sums[t] = sums0[t];
-  }
-  const bool reset = died || time_out;
-  const uint64_t hs = env_hash(seed, cnt->calls, i);
-  float obs_q[4] = {bq[0], bq[1], bq[2], bq[3]};
-
-  // _reset_idx (v4.py:920-1001): log (sum / own duration), reset events (pose, commands), defaults
-  const uint64_t lmask = __ballot(reset && lead);
-  if (reset) {
-    if (lead) {
-      const float dur = fmaxf(ep_len * step_dt, step_dt);
-      float* lr = log_row(q);
-#pragma unroll
-      for (int t = 0; t < ZB_V4_NUM_REWARD_TERMS; ++t) lr[t] = sums[t] / dur;
-      lr[ACC_NRES] = 1.f;
-      lr[ACC_DIED] = died ? 1.f : 0.f;
-      lr[ACC_TOUT] = time_out ? 1.f : 0.f;
-    }
-    cur_yaw = reset_pose(m, cfg, hs, p);
-    v4_resample(cfg, cnt, hs, 5, cur_yaw, cmd, tgt);
-    const float4 qr = q.dflt()[3];
-    const float qrel[4] = {qr.x, qr.y, qr.z, qr.w};
-    qmul(p.quat, qrel, obs_q);
-    float R[9];
-    qmat(p.quat, R);
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {  // feet_down_pos_last: pre-reset feet (v4.py:996) or reset pose's
-      const float4 fr = q.dflt()[4 + f];
-      const float v[3] = {fr.x, fr.y, fr.z};
-      float w3[3];
-      mv3(R, v, w3);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) down[f][a] = (cfg.reset_feet_refresh || blowup) ? p.pos[a] + w3[a] : feet[f][a];
-      f_last[f] = cfg.feet_f_last_init;
-      step_len[f] = 0.f;
-    }
-  }
-  // interval_command_resample (mode "interval", 3-6 s per env; after the resets, v4.py:426-439)
-  ileft -= step_dt;
-  if (ileft < 1e-6f) {
-    ileft = draw(hs, 8) * (cfg.cmd_interval_s[1] - cfg.cmd_interval_s[0]) + cfg.cmd_interval_s[0];
-    v4_resample(cfg, cnt, hs, 9, cur_yaw, cmd, tgt);
-  }
-  float he_obs;
-  {
-    float sn, cs;
-    sincos_r(tgt - cur_yaw, &sn, &cs);
-    he_obs = atan2f(sn, cs);
-  }
-  log_flush(q, lmask, acc);
-  store_wc_row(q, wc, N, i, reset, wc_row);
-  sp.mark(12);
-  if (writer) {
-    const Live live{reset};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { OUT(ZB_S_ROOT_POS + a) = p.pos[a]; OUT(ZB_S_ROOT_LINVEL + a) = p.lv[a]; OUT(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) OUT(ZB_S_ROOT_QUAT + a) = p.quat[a];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      OUT(ZB_S_JOINT_POS + j) = p.jq[j]; OUT(ZB_S_JOINT_VEL + j) = p.jqd[j];
-      OUT(ZB_V4_P_DELTA + j) = live(pr.pdel[j]); OUT(ZB_V4_ACTIONS + j) = live(pr.a_now[j]);
-    }
-    OUT(ZB_V4_COMMANDS) = cmd[0];
-    OUT(ZB_V4_COMMANDS + 1) = cmd[1];
-    OUT(ZB_V4_TARGET_YAW) = tgt;
-    OUT(ZB_V4_INTERVAL_LEFT) = ileft;
-    OUT(ZB_V4_CURRENT_YAW) = cur_yaw;
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) OUT(ZB_V4_FEET_DOWN_POS + 3 * f + a) = down[f][a];
-      OUT(ZB_V4_FEET_STEP_LEN + f) = step_len[f];
-      OUT(ZB_V4_FEET_F_LAST + f) = f_last[f];
-      OUT(ZB_V4_FEET_AIR_CUR + f) = live(air_cur[f]);
-      OUT(ZB_V4_FEET_CONTACT_CUR + f) = live(con_cur[f]);
-      OUT(ZB_V4_FEET_AIR_LAST + f) = live(air_last[f]);
-      OUT(ZB_V4_FEET_CONTACT_LAST + f) = live(con_last[f]);
-
-    }
-    sens_store<ZB_V4_HIST>(q, cst, 1, 0, ZB_V4_FEET_FZ_HIST, ZB_V4_UNDES_FMAX_HIST, cfg.decimation, reset,
-                           [&](int row, float v) { OUT(row) = v; });
-    OUT(ZB_V4_EP_LEN) = live(ep_len);
-#pragma unroll
-    for (int t = 0; t < ZB_V4_NUM_REWARD_TERMS; ++t) OUT(ZB_V4_EP_SUMS + t) = live(sums[t]);
-
-    // _get_observations (v4.py:851-881)
-    float* o = &q.stg(ZB_V4_STATE_DIM);
-    o[0] = obs_q[0]; o[1] = obs_q[1]; o[2] = obs_q[2]; o[3] = obs_q[3];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) {
-      o[4 + j] = p.jq[j] - m->default_joint_pos[j];
-      o[10 + j] = p.jqd[j];
-      o[16 + j] = live(pr.a_now[j]);
-    }
-    o[22] = cmd[0];
-    o[23] = he_obs;
-    stage_result<ZB_V4_STATE_DIM, ZB_V4_OBS_DIM>(q, reward, died, time_out);
-  }
-  step_finish<ZB_V4_STATE_DIM, ZB_V4_OBS_DIM>(q, N, st, obs, rew, term, trunc, done, sp);
-}
-
-// explicit resets / construction (init = 1 also draws the interval-event timers, as Isaac Lab's
-// EventManager does when it is created): log, reset events, defaults; one thread per env
-__global__ void zb_v4_reset_kernel(const zb_model* __restrict__ mg, const float4* __restrict__ links, zb_task_cfg cfg,
-                                   int N, float* __restrict__ st, const int32_t* __restrict__ ids, int n,
-                                   float* __restrict__ acc, const Counters* __restrict__ cnt, uint64_t seed, int init) {
-  MP m = to_mp(mg);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int i = ids ? ids[t] : t;
-  if (i < 0 || i >= N) return;
-  const float step_dt = cfg.sim_dt * (float)cfg.decimation;
-  if (!init) {
-    const float dur = fmaxf(ST(ZB_V4_EP_LEN) * step_dt, step_dt);
-#pragma unroll
-    for (int k = 0; k < ZB_V4_NUM_REWARD_TERMS; ++k) atomicAdd(&acc_slot(acc, t)[k], ST(ZB_V4_EP_SUMS + k) / dur);
-    atomicAdd(&acc_slot(acc, t)[ACC_NRES], 1.f);
-  }
-  float pre[2][3];  // the pre-reset feet (the spawn pose at construction)
-  if (!cfg.reset_feet_refresh) {
-    Phys p0;
-    if (init) phys_default(m, p0);
-    else load_phys(st, N, i, p0);
-    feet_world(m, p0, pre);
-  }
-  Phys p;
-  const uint64_t hs = env_hash(seed, cnt->calls, i);
-  const float cur_yaw = reset_pose(m, cfg, hs, p);
-  float cmd[2], tgt;
-  v4_resample(cfg, cnt, hs, 5, cur_yaw, cmd, tgt);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { ST(ZB_S_ROOT_POS + a) = p.pos[a]; ST(ZB_S_ROOT_LINVEL + a) = p.lv[a]; ST(ZB_S_ROOT_ANGVEL + a) = p.av[a]; }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) ST(ZB_S_ROOT_QUAT + a) = p.quat[a];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) {
-    ST(ZB_S_JOINT_POS + j) = p.jq[j]; ST(ZB_S_JOINT_VEL + j) = p.jqd[j];
-    ST(ZB_V4_P_DELTA + j) = 0.f; ST(ZB_V4_ACTIONS + j) = 0.f;
-  }
-  ST(ZB_V4_COMMANDS) = cmd[0];
-  ST(ZB_V4_COMMANDS + 1) = cmd[1];
-  ST(ZB_V4_TARGET_YAW) = tgt;
-  ST(ZB_V4_CURRENT_YAW) = cur_yaw;
-  if (init) ST(ZB_V4_INTERVAL_LEFT) = draw(hs, 8) * (cfg.cmd_interval_s[1] - cfg.cmd_interval_s[0]) + cfg.cmd_interval_s[0];
-  float R[9];
-  qmat(p.quat, R);
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const float4 fr = links[DFLT_OFF + 4 + f];
-    const float v[3] = {fr.x, fr.y, fr.z};
-    float w3[3];
-    mv3(R, v, w3);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) ST(ZB_V4_FEET_DOWN_POS + 3 * f + a) = cfg.reset_feet_refresh ? p.pos[a] + w3[a] : pre[f][a];
-    ST(ZB_V4_FEET_STEP_LEN + f) = 0.f;
-    ST(ZB_V4_FEET_F_LAST + f) = cfg.feet_f_last_init;
-    ST(ZB_V4_FEET_AIR_CUR + f) = 0.f;
-    ST(ZB_V4_FEET_CONTACT_CUR + f) = 0.f;
-    ST(ZB_V4_FEET_AIR_LAST + f) = 0.f;
-    ST(ZB_V4_FEET_CONTACT_LAST + f) = 0.f;
-#pragma unroll
-    for (int h = 0; h < ZB_V4_HIST; ++h) ST(ZB_V4_FEET_FZ_HIST + 2 * h + f) = 0.f;
-  }
-#pragma unroll
-  for (int h = 0; h < ZB_V4_HIST; ++h) ST(ZB_V4_UNDES_FMAX_HIST + h) = 0.f;
-  ST(ZB_V4_EP_LEN) = 0.f;
-#pragma unroll
-  for (int k = 0; k < ZB_V4_NUM_REWARD_TERMS; ++k) ST(ZB_V4_EP_SUMS + k) = 0.f;
-}
-
-// the observation of env i's current state (v4.py _get_observations) into the row o (out of line: obs_row)
-__device__ __noinline__ void v4_obs_row(const zb_model* mg, int N, const float* st, int i, float* o) {
-  MP m = to_mp(mg);
-  Phys p;
-  load_phys(st, N, i, p);
-  Kin k;
-  fk(m, p, k);
-  float bp[3], bq[4];
-  link_pose(m, k, 6, bp, bq);
-  o[0] = bq[0]; o[1] = bq[1]; o[2] = bq[2]; o[3] = bq[3];
-#pragma unroll
-  for (int j = 0; j < ND; ++j) {
-    o[4 + j] = p.jq[j] - m->default_joint_pos[j];
-    o[10 + j] = p.jqd[j];
-    o[16 + j] = st[(size_t)(ZB_V4_ACTIONS + j) * N + i];
-  }
-  o[22] = st[(size_t)ZB_V4_COMMANDS * N + i];
-  float sn, cs;
-  sincos_r(st[(size_t)ZB_V4_TARGET_YAW * N + i] - st[(size_t)ZB_V4_CURRENT_YAW * N + i], &sn, &cs);
-  o[23] = atan2f(sn, cs);
-}
-
-__global__ void zb_v4_observe_kernel(const zb_model* __restrict__ mg, int N, const float* __restrict__ st,
-                                     float* __restrict__ obs) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  v4_obs_row(mg, N, st, i, obs + (size_t)i * ZB_V4_OBS_DIM);
-}
-
+#include "sim_standup.h"
+#include "sim_walking_v4.h"
 #include "sim_manager.h"
 
 // =========================================================================== critic observations
@@ -4773,21 +4009,22 @@ __global__ void zb_finalize_kernel(int N, float* __restrict__ st, float* __restr
 #ifndef ZB_OCC1_DEFAULT
 #define ZB_OCC1_DEFAULT 1
 #endif
+// Every device pointer starts null, so a handle that zb_create gave up on half-way is safe to zb_destroy.
 struct zb_sim {
-  int device;
-  int n;
-  uint64_t seed;
-  int task;           // ZB_TASK_*
-  int state_dim;      // ZB_STATE_DIM / ZB_SU_STATE_DIM
-  Counters* d_cnt;    // device counters (graph-replay safe)
-  zb_task_cfg cfg;
-  zb_model* d_model;
-  float4* d_links;  // per-link collision table [NL][LINK4] (detect)
-  float* d_state;
+  int device = 0;
+  int n = 0;
+  uint64_t seed = 0;
+  int task = 0;           // ZB_TASK_*
+  int state_dim = 0;      // ZB_STATE_DIM / ZB_SU_STATE_DIM
+  Counters* d_cnt = nullptr;    // device counters (graph-replay safe)
+  zb_task_cfg cfg = {};
+  zb_model* d_model = nullptr;
+  float4* d_links = nullptr;  // per-link collision table [NL][LINK4] (detect)
+  float* d_state = nullptr;
   float* d_wc = nullptr;  // persistent self-contact cache: ZB_WARM_ROWS x n
-  float* d_acc;
-  float* d_log_means;
-  int32_t* d_log_counts;
+  float* d_acc = nullptr;
+  float* d_log_means = nullptr;
+  int32_t* d_log_counts = nullptr;
   float* u_log_means = nullptr;     // optional caller buffers (zb_set_log_buffers)
   int32_t* u_log_counts = nullptr;
   float* u_log_acc = nullptr;       // optional caller accumulator (zb_set_log_accumulator)
@@ -4852,6 +4089,24 @@ void zb_launch(F kernel, int blocks, hipStream_t s, hipEvent_t e0, hipEvent_t e1
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WGT), 0, s, args...);
 }
 
+// rows x n floats between a caller's device buffer and one of the handle's (the get / set pairs)
+static int copy_rows(float* dst, const float* src, int rows, zb_handle h, void* stream, const char* what) {
+  HIPCHK(hipMemcpyAsync(dst, src, sizeof(float) * (size_t)rows * h->n, hipMemcpyDeviceToDevice, (hipStream_t)stream), what);
+  return 0;
+}
+
+// the self-contact cache of cnt envs (ids, or the first cnt) back to "no contact": a cold start next step
+static int wc_fill(zb_handle h, const int32_t* ids, int cnt, hipStream_t s) {
+  zb_wc_fill_kernel<<<(cnt * ZB_WARM_ROWS + 255) / 256, 256, 0, s>>>(h->n, h->d_wc, ids, cnt);
+  return launch_check("zb_wc_fill_kernel");
+}
+
+// one per-link friction row block of the state from mu[n][NL], or filled with one value (mu null)
+static int friction_rows(zb_handle h, const float* mu, float fill, int row, hipStream_t s) {
+  zb_su_friction_kernel<<<(h->n * NL + 255) / 256, 256, 0, s>>>(h->n, h->d_state, mu, fill, row);
+  return launch_check("zb_su_friction_kernel");
+}
+
 // The task table: what the host side knows about each task, one row per ZB_TASK_*.
 struct TaskRow {
   int state_dim, ep_row;  // state rows; the EP_LEN row (zb_finalize_kernel)
@@ -4864,6 +4119,7 @@ struct TaskRow {
   bool init_calls;        // the construction reset draws at RNG position 0; later calls start at 1
   void (*critic)(zb_handle, float*, hipStream_t);
   int (*init)(zb_handle);                                          // construction reset (checked inside)
+  int (*side)(zb_handle, const zb_model*);                         // the task's side buffers, after init; or null
   void (*reset)(zb_handle, const int32_t*, int, hipStream_t, int);  // (ids, count, stream, init)
   void (*observe)(zb_handle, float*, hipStream_t);
 };
@@ -4899,27 +4155,48 @@ static void reset_m(zb_handle h, const int32_t* ids, int cnt, hipStream_t s, int
 }
 static int init_v2(zb_handle h) { reset_v2(h, nullptr, h->n, 0, 1); return launch_check("zb_reset_kernel"); }
 static int init_su(zb_handle h) {
-  const float fill[2] = {h->cfg.friction, h->cfg.friction_dynamic};
-  const int rows[2] = {ZB_SU_LINK_MU, ZB_SU_LINK_MU_D};
-  for (int k = 0; k < 2; ++k) {
-    zb_su_friction_kernel<<<(h->n * NL + 255) / 256, 256>>>(h->n, h->d_state, nullptr, fill[k], rows[k]);
-    const int rc = launch_check("zb_su_friction_kernel");
-    if (rc) return rc;
-  }
+  int rc = friction_rows(h, nullptr, h->cfg.friction, ZB_SU_LINK_MU, 0);
+  if (!rc) rc = friction_rows(h, nullptr, h->cfg.friction_dynamic, ZB_SU_LINK_MU_D, 0);
+  if (rc) return rc;
   reset_su(h, nullptr, h->n, 0, 1);
   return launch_check("zb_su_reset_kernel");
 }
 static int init_v4(zb_handle h) { reset_v4(h, nullptr, h->n, 0, 1); return launch_check("zb_v4_reset_kernel"); }
 static int init_m(zb_handle h) { reset_m(h, nullptr, h->n, 0, 1); return launch_check("zb_m_reset_kernel"); }
 
-static void observe_v2(zb_handle h, float* obs, hipStream_t s) {
-  zb_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->n, h->d_state, obs);
+// The manager task's side buffers, allocated last: the event state (zero while events are off), the per-env base
+// inertia (the nominal rows while the feature is off) and its flag, the term state and configuration (zero).
+static int side_m(zb_handle h, const zb_model* m) {
+  const size_t n = (size_t)h->n;
+  HIPCHK(hipMalloc(&h->d_ev, sizeof(float) * ZB_ME_STATE_DIM * n), "hipMalloc event state");
+  HIPCHK(hipMemset(h->d_ev, 0, sizeof(float) * ZB_ME_STATE_DIM * n), "hipMemset event state");
+  if (m->api_root_link != m->base_link)
+    return set_err(-1, "zb_create: the manager task's articulation root is its base link", hipSuccess);
+  std::vector<float4> rows(n * 4);
+  const int bl = m->base_link;
+  const float* I = m->body_inertia[BASE_BODY];
+  for (size_t i = 0; i < n; ++i) {
+    float4* t = rows.data() + i * 4;
+    t[0] = make_float4(m->body_com[BASE_BODY][0], m->body_com[BASE_BODY][1], m->body_com[BASE_BODY][2], m->body_mass[BASE_BODY]);
+    t[1] = make_float4(I[0], I[1], I[2], I[3]);
+    t[2] = make_float4(I[4], I[5], 0.f, 0.f);
+    t[3] = make_float4(m->link_com[bl][0], m->link_com[bl][1], m->link_com[bl][2], 0.f);
+  }
+  HIPCHK(hipMalloc(&h->d_bi, sizeof(float4) * rows.size()), "hipMalloc base inertia");
+  HIPCHK(hipMemcpy(h->d_bi, rows.data(), sizeof(float4) * rows.size(), hipMemcpyHostToDevice), "hipMemcpy base inertia");
+  HIPCHK(hipMalloc(&h->d_bi_flag, sizeof(int)), "hipMalloc base inertia flag");
+  HIPCHK(hipMemset(h->d_bi_flag, 0, sizeof(int)), "hipMemset base inertia flag");
+  HIPCHK(hipMalloc(&h->d_tm, sizeof(float) * ZB_MT_STATE_DIM * n), "hipMalloc term state");
+  HIPCHK(hipMemset(h->d_tm, 0, sizeof(float) * ZB_MT_STATE_DIM * n), "hipMemset term state");
+  HIPCHK(hipMalloc(&h->d_tmc, sizeof(zb_manager_terms)), "hipMalloc term cfg");
+  HIPCHK(hipMemset(h->d_tmc, 0, sizeof(zb_manager_terms)), "hipMemset term cfg");
+  return 0;
 }
-static void observe_su(zb_handle h, float* obs, hipStream_t s) {
-  zb_su_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->n, h->d_state, obs);
-}
-static void observe_v4(zb_handle h, float* obs, hipStream_t s) {
-  zb_v4_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->n, h->d_state, obs);
+
+// the observe kernels that read the state alone: walking v2, stand-up, walking v4
+template <void (*kKernel)(const zb_model*, int, const float*, float*)>
+static void observe_task(zb_handle h, float* obs, hipStream_t s) {
+  kKernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->n, h->d_state, obs);
 }
 static void observe_m(zb_handle h, float* obs, hipStream_t s) {
   zb_m_observe_kernel<<<(h->n + 255) / 256, 256, 0, s>>>(h->d_model, h->cfg, h->n, h->d_state, obs, h->d_cnt, h->seed);
@@ -4927,13 +4204,13 @@ static void observe_m(zb_handle h, float* obs, hipStream_t s) {
 
 static const TaskRow kTasks[] = {
     /* ZB_TASK_WALKING_V2 */ {ZB_STATE_DIM, ZB_S_EP_LEN, true, -1, -1, true, false,
-                              critic_task<ZB_TASK_WALKING_V2>, init_v2, reset_v2, observe_v2},
+                              critic_task<ZB_TASK_WALKING_V2>, init_v2, nullptr, reset_v2, observe_task<zb_observe_kernel>},
     /* ZB_TASK_STANDUP_V0 */ {ZB_SU_STATE_DIM, ZB_SU_EP_LEN, false, ZB_SU_LINK_MU, ZB_SU_LINK_MU_D, true, true,
-                              critic_task<ZB_TASK_STANDUP_V0>, init_su, reset_su, observe_su},
+                              critic_task<ZB_TASK_STANDUP_V0>, init_su, nullptr, reset_su, observe_task<zb_su_observe_kernel>},
     /* ZB_TASK_WALKING_V4 */ {ZB_V4_STATE_DIM, ZB_V4_EP_LEN, false, -1, -1, false, true,
-                              critic_task<ZB_TASK_WALKING_V4>, init_v4, reset_v4, observe_v4},
+                              critic_task<ZB_TASK_WALKING_V4>, init_v4, nullptr, reset_v4, observe_task<zb_v4_observe_kernel>},
     /* ZB_TASK_MANAGER_V0 */ {ZB_M_STATE_DIM, ZB_M_EP_LEN, true, ZB_M_LINK_MU, ZB_M_LINK_MU_D, false, true,
-                              critic_task<ZB_TASK_MANAGER_V0>, init_m, reset_m, observe_m},
+                              critic_task<ZB_TASK_MANAGER_V0>, init_m, side_m, reset_m, observe_m},
 };
 constexpr int kNumTasks = sizeof(kTasks) / sizeof(kTasks[0]);
 static_assert(ZB_TASK_WALKING_V2 == 0 && ZB_TASK_STANDUP_V0 == 1 && ZB_TASK_WALKING_V4 == 2 && ZB_TASK_MANAGER_V0 == 3,
@@ -4978,13 +4255,8 @@ static MBuild m_build(const zb_sim* h) {
   return h->tm_on ? MBuild::terms : h->bi_on ? MBuild::dr : h->ev_on ? MBuild::events : MBuild::plain;
 }
 
-extern "C" {
-
-const char* zb_last_error(void) { return g_err; }
-
-int zb_num_envs(zb_handle h) { return h ? h->n : -1; }
-
-int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_device, uint64_t seed, zb_handle* out) {
+// zb_create in steps. validate: the arguments, the model against the compiled-in chain, the cfg against the task.
+static int validate(const zb_model* m, const zb_task_cfg* c, int num_envs, zb_handle* out) {
   if (!m || !c || !out || num_envs <= 0) return set_err(-1, "zb_create", hipSuccess);
   for (int l = 0; l < NL; ++l)
     if (m->link_body[l] != link_body(l)) return set_err(-1, "zb_create: model topology != compiled ZBOT-6 chain", hipSuccess);
@@ -5019,33 +4291,82 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
       if (c->reward_scales[t] != 0.f && !((c->reward_active >> t) & 1u))
         return set_err(-1, "zb_create: reward term with a non-zero scale but its reward_active bit clear", hipSuccess);
   if (c->task == ZB_TASK_STANDUP_V0 && c->center_z_period < 1) return set_err(-1, "zb_create: center_z_period", hipSuccess);
-  HIPCHK(hipSetDevice(hip_device), "hipSetDevice");
-  zb_sim* h = new zb_sim();
-  h->device = hip_device;
-  h->n = num_envs;
-  h->seed = seed;
-  h->task = c->task;
-  h->state_dim = kTasks[c->task].state_dim;
-  h->d_cnt = nullptr;
-  h->cfg = *c;
-  {
-    double mass = 0.0;
-    for (int b = 0; b < NB; ++b) mass += m->body_mass[b];
-    h->inv_weight = (float)(1.0 / (mass * (double)c->gravity));
+  return 0;
+}
+
+// build_link_table: the host copy of d_links (per-link shapes; joint frames, body inertias, self-pair codes)
+static void build_link_table(const zb_model* m, float4 (&tab)[LNK4]) {
+  memset(tab, 0, sizeof(tab));
+  for (int l = 0; l < NL; ++l) {
+    float4* t = tab + l * LINK4;
+    t[0] = make_float4(m->link_bound[l][0], m->link_bound[l][1], m->link_bound[l][2], m->link_bound[l][3]);
+    for (int ci = 0; ci < 2; ++ci)
+      for (int v = 0; v < 3; ++v) {
+        const float* c = m->link_circle[l][ci] + 3 * v;
+        // C.w = 1: a mated face duplicating a lower link's circle (ground detection skips it)
+        t[1 + 3 * ci + v] = make_float4(c[0], c[1], c[2], v == 0 && ((m->link_circle_dup[l] >> ci) & 1) ? 1.f : 0.f);
+      }
+    // self-collision core circles (kCoreM into the shape along each circle's normal, radius
+    // r - kCoreM; the same rule as the oracle's load_mdl): {centre, semi-axis scale}
+    double mid[3], rad = 0.0;
+    for (int a = 0; a < 3; ++a) mid[a] = 0.5 * ((double)m->link_circle[l][0][a] + m->link_circle[l][1][a]);
+    for (int ci = 0; ci < 2; ++ci) {
+      const float* c = m->link_circle[l][ci];
+      const float* o = m->link_circle[l][1 - ci];
+      double n[3] = {(double)c[4] * c[8] - (double)c[5] * c[7], (double)c[5] * c[6] - (double)c[3] * c[8],
+                     (double)c[3] * c[7] - (double)c[4] * c[6]};
+      const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+      const double r = sqrt((double)c[3] * c[3] + (double)c[4] * c[4] + (double)c[5] * c[5]);
+      const double to = n[0] * (o[0] - c[0]) + n[1] * (o[1] - c[1]) + n[2] * (o[2] - c[2]);
+      const double sg = to < 0.0 ? -1.0 : 1.0;
+      t[7 + ci] = make_float4((float)(c[0] + sg * kCoreM * n[0] / nn), (float)(c[1] + sg * kCoreM * n[1] / nn),
+                              (float)(c[2] + sg * kCoreM * n[2] / nn), (float)((r - kCoreM) / r));
+      const double dc = sqrt((c[0] - mid[0]) * (c[0] - mid[0]) + (c[1] - mid[1]) * (c[1] - mid[1]) +
+                             (c[2] - mid[2]) * (c[2] - mid[2]));
+      rad = fmax(rad, dc + r);
+    }
+    // bounding sphere of the whole shape
+    t[9] = make_float4((float)mid[0], (float)mid[1], (float)mid[2], (float)(rad + 1e-6));
+    // self-collision broadphase: the core hull lies in the capsule of its two core circle centres
+    // with the larger core radius (+ 1 um)
+    {
+      double rc = 0.0;
+      for (int ci = 0; ci < 2; ++ci) {
+        const float* c = m->link_circle[l][ci];
+        rc = fmax(rc, sqrt((double)c[3] * c[3] + (double)c[4] * c[4] + (double)c[5] * c[5]) - kCoreM);
+      }
+      t[2].w = (float)(rc + 1e-6);
+    }
   }
+  for (int j = 0; j < ND; ++j) {
+    float4* t = tab + JT_OFF + j * 5;
+    const float* r = m->joint_parent_rot[j];
+    t[0] = make_float4(r[0], r[1], r[2], r[3]);
+    t[1] = make_float4(m->joint_parent_pos[j][0], m->joint_parent_pos[j][1], m->joint_parent_pos[j][2], 0.f);
+    t[2] = make_float4(m->joint_child_pos[j][0], m->joint_child_pos[j][1], m->joint_child_pos[j][2], 0.f);
+    const float* c = m->joint_child_rot[j];
+    t[3] = make_float4(c[0], c[1], c[2], c[3]);
+    const float w = r[0], x = r[1], y = r[2], z = r[3];  // third column of R(jpr)
+    t[4] = make_float4(2.f * (x * z + w * y), 2.f * (y * z - w * x), 1.f - 2.f * (x * x + y * y), 0.f);
+  }
+  for (int b = 0; b < NB; ++b) {
+    float4* t = tab + BT_OFF + b * 3;
+    const float* I = m->body_inertia[b];
+    t[0] = make_float4(m->body_com[b][0], m->body_com[b][1], m->body_com[b][2], m->body_mass[b]);
+    t[1] = make_float4(I[0], I[1], I[2], I[3]);
+    t[2] = make_float4(I[4], I[5], 0.f, 0.f);
+  }
+  int* pc = reinterpret_cast<int*>(tab + NL * LINK4);
+  for (int p = 0; p < m->num_self_pairs; ++p) pc[p] = 16 * m->self_pairs[p][0] + m->self_pairs[p][1];
+}
+
+// allocate: every task's device buffers, the model, the counters and the link table up; the rest zero
+static int allocate(zb_sim* h, const zb_model* m) {
+  const zb_task_cfg* c = &h->cfg;
   HIPCHK(hipMalloc(&h->d_model, sizeof(zb_model)), "hipMalloc model");
-  HIPCHK(hipMalloc(&h->d_state, sizeof(float) * (size_t)h->state_dim * num_envs), "hipMalloc state");
+  HIPCHK(hipMalloc(&h->d_state, sizeof(float) * (size_t)h->state_dim * h->n), "hipMalloc state");
   HIPCHK(hipMalloc(&h->d_acc, sizeof(float) * ACC_SLOTS * ACC_STRIDE), "hipMalloc acc");
   HIPCHK(hipMalloc(&h->d_cnt, sizeof(Counters)), "hipMalloc counters");
-  {
-    // one wave per SIMD at <= 4096 envs (<= one wave per SIMD anyway): ZB_OCC1=0/1 overrides (only
-    // an explicit "1" / "0": an empty value or "false" does not)
-    const char* oc = getenv("ZB_OCC1");
-    const int oc_on = oc && oc[0] == '1' && oc[1] == 0, oc_off = oc && oc[0] == '0' && oc[1] == 0;
-    h->occ1 = oc_on || (!oc_off && ZB_OCC1_DEFAULT && num_envs <= 4096);
-    const char* nf = getenv("ZB_DIAG_NO_FINALIZE");
-    h->diag_no_finalize = nf && nf[0] == '1' && nf[1] == 0;
-  }
   {
     Counters c0;
     memset(&c0, 0, sizeof(c0));
@@ -5057,121 +4378,76 @@ int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_dev
   HIPCHK(hipMalloc(&h->d_log_means, sizeof(float) * ZB_LOG_LEN), "hipMalloc log");
   HIPCHK(hipMalloc(&h->d_log_counts, sizeof(int32_t) * ZB_LOG_COUNTS), "hipMalloc log");
   HIPCHK(hipMemcpy(h->d_model, m, sizeof(zb_model), hipMemcpyHostToDevice), "hipMemcpy model");
-  {
-    float4 tab[LNK4];
-    memset(tab, 0, sizeof(tab));
-    for (int l = 0; l < NL; ++l) {
-      float4* t = tab + l * LINK4;
-      t[0] = make_float4(m->link_bound[l][0], m->link_bound[l][1], m->link_bound[l][2], m->link_bound[l][3]);
-      for (int ci = 0; ci < 2; ++ci)
-        for (int v = 0; v < 3; ++v) {
-          const float* c = m->link_circle[l][ci] + 3 * v;
-          // C.w = 1: a mated face duplicating a lower link's circle (ground detection skips it)
-          t[1 + 3 * ci + v] = make_float4(c[0], c[1], c[2], v == 0 && ((m->link_circle_dup[l] >> ci) & 1) ? 1.f : 0.f);
-        }
-      // self-collision core circles (kCoreM into the shape along each circle's normal, radius
-      // r - kCoreM; the same rule as the oracle's load_mdl): {centre, semi-axis scale}
-      double mid[3], rad = 0.0;
-      for (int a = 0; a < 3; ++a) mid[a] = 0.5 * ((double)m->link_circle[l][0][a] + m->link_circle[l][1][a]);
-      for (int ci = 0; ci < 2; ++ci) {
-        const float* c = m->link_circle[l][ci];
-        const float* o = m->link_circle[l][1 - ci];
-        double n[3] = {(double)c[4] * c[8] - (double)c[5] * c[7], (double)c[5] * c[6] - (double)c[3] * c[8],
-                       (double)c[3] * c[7] - (double)c[4] * c[6]};
-        const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-        const double r = sqrt((double)c[3] * c[3] + (double)c[4] * c[4] + (double)c[5] * c[5]);
-        const double to = n[0] * (o[0] - c[0]) + n[1] * (o[1] - c[1]) + n[2] * (o[2] - c[2]);
-        const double sg = to < 0.0 ? -1.0 : 1.0;
-        t[7 + ci] = make_float4((float)(c[0] + sg * kCoreM * n[0] / nn), (float)(c[1] + sg * kCoreM * n[1] / nn),
-                                (float)(c[2] + sg * kCoreM * n[2] / nn), (float)((r - kCoreM) / r));
-        const double dc = sqrt((c[0] - mid[0]) * (c[0] - mid[0]) + (c[1] - mid[1]) * (c[1] - mid[1]) +
-                               (c[2] - mid[2]) * (c[2] - mid[2]));
-        rad = fmax(rad, dc + r);
-      }
-      // bounding sphere of the whole shape
-      t[9] = make_float4((float)mid[0], (float)mid[1], (float)mid[2], (float)(rad + 1e-6));
-      // self-collision broadphase: the core hull lies in the capsule of its two core circle centres
-      // with the larger core radius (+ 1 um)
-      {
-        double rc = 0.0;
-        for (int ci = 0; ci < 2; ++ci) {
-          const float* c = m->link_circle[l][ci];
-          rc = fmax(rc, sqrt((double)c[3] * c[3] + (double)c[4] * c[4] + (double)c[5] * c[5]) - kCoreM);
-        }
-        t[2].w = (float)(rc + 1e-6);
-      }
-    }
-    for (int j = 0; j < ND; ++j) {
-      float4* t = tab + JT_OFF + j * 5;
-      const float* r = m->joint_parent_rot[j];
-      t[0] = make_float4(r[0], r[1], r[2], r[3]);
-      t[1] = make_float4(m->joint_parent_pos[j][0], m->joint_parent_pos[j][1], m->joint_parent_pos[j][2], 0.f);
-      t[2] = make_float4(m->joint_child_pos[j][0], m->joint_child_pos[j][1], m->joint_child_pos[j][2], 0.f);
-      const float* c = m->joint_child_rot[j];
-      t[3] = make_float4(c[0], c[1], c[2], c[3]);
-      const float w = r[0], x = r[1], y = r[2], z = r[3];  // third column of R(jpr)
-      t[4] = make_float4(2.f * (x * z + w * y), 2.f * (y * z - w * x), 1.f - 2.f * (x * x + y * y), 0.f);
-    }
-    for (int b = 0; b < NB; ++b) {
-      float4* t = tab + BT_OFF + b * 3;
-      const float* I = m->body_inertia[b];
-      t[0] = make_float4(m->body_com[b][0], m->body_com[b][1], m->body_com[b][2], m->body_mass[b]);
-      t[1] = make_float4(I[0], I[1], I[2], I[3]);
-      t[2] = make_float4(I[4], I[5], 0.f, 0.f);
-    }
-    int* pc = reinterpret_cast<int*>(tab + NL * LINK4);
-    for (int p = 0; p < m->num_self_pairs; ++p) pc[p] = 16 * m->self_pairs[p][0] + m->self_pairs[p][1];
-    HIPCHK(hipMalloc(&h->d_links, sizeof(tab)), "hipMalloc links");
-    HIPCHK(hipMemcpy(h->d_links, tab, sizeof(tab), hipMemcpyHostToDevice), "hipMemcpy links");
-  }
-  HIPCHK(hipMemset(h->d_state, 0, sizeof(float) * (size_t)h->state_dim * num_envs), "hipMemset state");
+  float4 tab[LNK4];
+  build_link_table(m, tab);
+  HIPCHK(hipMalloc(&h->d_links, sizeof(tab)), "hipMalloc links");
+  HIPCHK(hipMemcpy(h->d_links, tab, sizeof(tab), hipMemcpyHostToDevice), "hipMemcpy links");
+  HIPCHK(hipMemset(h->d_state, 0, sizeof(float) * (size_t)h->state_dim * h->n), "hipMemset state");
   HIPCHK(hipMemset(h->d_log_means, 0, sizeof(float) * ZB_LOG_LEN), "hipMemset log");
   HIPCHK(hipMemset(h->d_log_counts, 0, sizeof(int32_t) * ZB_LOG_COUNTS), "hipMemset log");
   HIPCHK(hipMemset(h->d_acc, 0, sizeof(float) * ACC_SLOTS * ACC_STRIDE), "hipMemset acc");
-  // start at the default pose (ep_len 0, as after construction; reset() randomises it)
+  return 0;
+}
+
+// construction_reset: the default pose (ep_len 0; reset() randomises it) and a cold contact cache
+static int construction_reset(zb_sim* h) {
   zb_derive_kernel<<<1, 1>>>(h->d_model, h->d_links);
   int rc = launch_check("zb_derive_kernel");
-  if (rc) return rc;
-  rc = kTasks[h->task].init(h);
+  if (!rc) rc = kTasks[h->task].init(h);
   if (rc) return rc;
   if (kTasks[h->task].init_calls) {
     const uint64_t one = 1;
     HIPCHK(hipMemcpy(&h->d_cnt->calls, &one, sizeof(one), hipMemcpyHostToDevice), "hipMemcpy counters");
   }
   HIPCHK(hipMemset(h->d_acc, 0, sizeof(float) * ACC_SLOTS * ACC_STRIDE), "hipMemset acc");
+  HIPCHK(hipMalloc(&h->d_wc, sizeof(float) * ZB_WARM_ROWS * (size_t)h->n), "hipMalloc contact cache");
+  return wc_fill(h, nullptr, h->n, 0);
+}
+
+// a handle under construction: destroyed, device buffers included, on every return but the last
+struct CreateGuard {
+  zb_sim* h;
+  ~CreateGuard() { zb_destroy(h); }
+};
+
+extern "C" {
+
+const char* zb_last_error(void) { return g_err; }
+
+int zb_num_envs(zb_handle h) { return h ? h->n : -1; }
+
+int zb_create(const zb_model* m, const zb_task_cfg* c, int num_envs, int hip_device, uint64_t seed, zb_handle* out) {
+  int rc = validate(m, c, num_envs, out);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(hip_device), "hipSetDevice");
+  CreateGuard own = {new zb_sim()};
+  zb_sim* h = own.h;
+  h->device = hip_device;
+  h->n = num_envs;
+  h->seed = seed;
+  h->task = c->task;
+  h->state_dim = kTasks[c->task].state_dim;
+  h->cfg = *c;
   {
-    HIPCHK(hipMalloc(&h->d_wc, sizeof(float) * ZB_WARM_ROWS * (size_t)num_envs), "hipMalloc contact cache");
-    zb_wc_fill_kernel<<<(num_envs * ZB_WARM_ROWS + 255) / 256, 256>>>(num_envs, h->d_wc, nullptr, num_envs);
-    rc = launch_check("zb_wc_fill_kernel");
-    if (rc) return rc;
+    double mass = 0.0;
+    for (int b = 0; b < NB; ++b) mass += m->body_mass[b];
+    h->inv_weight = (float)(1.0 / (mass * (double)c->gravity));
   }
-  if (h->task == ZB_TASK_MANAGER_V0) {  // the event state (include/zbot_manager_events.h): zero while events are off
-    HIPCHK(hipMalloc(&h->d_ev, sizeof(float) * ZB_ME_STATE_DIM * (size_t)num_envs), "hipMalloc event state");
-    HIPCHK(hipMemset(h->d_ev, 0, sizeof(float) * ZB_ME_STATE_DIM * (size_t)num_envs), "hipMemset event state");
-    // the per-env base inertia (include/zbot_base_inertia.h): the nominal rows while the feature is off
-    if (m->api_root_link != m->base_link)
-      return set_err(-1, "zb_create: the manager task's articulation root is its base link", hipSuccess);
-    std::vector<float4> rows((size_t)num_envs * 4);
-    const int bl = m->base_link;
-    const float* I = m->body_inertia[BASE_BODY];
-    for (int i = 0; i < num_envs; ++i) {
-      float4* t = rows.data() + (size_t)i * 4;
-      t[0] = make_float4(m->body_com[BASE_BODY][0], m->body_com[BASE_BODY][1], m->body_com[BASE_BODY][2], m->body_mass[BASE_BODY]);
-      t[1] = make_float4(I[0], I[1], I[2], I[3]);
-      t[2] = make_float4(I[4], I[5], 0.f, 0.f);
-      t[3] = make_float4(m->link_com[bl][0], m->link_com[bl][1], m->link_com[bl][2], 0.f);
-    }
-    HIPCHK(hipMalloc(&h->d_bi, sizeof(float4) * rows.size()), "hipMalloc base inertia");
-    HIPCHK(hipMemcpy(h->d_bi, rows.data(), sizeof(float4) * rows.size(), hipMemcpyHostToDevice), "hipMemcpy base inertia");
-    HIPCHK(hipMalloc(&h->d_bi_flag, sizeof(int)), "hipMalloc base inertia flag");
-    HIPCHK(hipMemset(h->d_bi_flag, 0, sizeof(int)), "hipMemset base inertia flag");
-    // the term state (include/zbot_manager_terms.h): zero while no term is active
-    HIPCHK(hipMalloc(&h->d_tm, sizeof(float) * ZB_MT_STATE_DIM * (size_t)num_envs), "hipMalloc term state");
-    HIPCHK(hipMemset(h->d_tm, 0, sizeof(float) * ZB_MT_STATE_DIM * (size_t)num_envs), "hipMemset term state");
-    HIPCHK(hipMalloc(&h->d_tmc, sizeof(zb_manager_terms)), "hipMalloc term cfg");
-    HIPCHK(hipMemset(h->d_tmc, 0, sizeof(zb_manager_terms)), "hipMemset term cfg");
+  {
+    // one wave per SIMD at <= 4096 envs (<= one wave per SIMD anyway): ZB_OCC1=0/1 overrides (only
+    // an explicit "1" / "0": an empty value or "false" does not)
+    const char* oc = getenv("ZB_OCC1");
+    const int oc_on = oc && oc[0] == '1' && oc[1] == 0, oc_off = oc && oc[0] == '0' && oc[1] == 0;
+    h->occ1 = oc_on || (!oc_off && ZB_OCC1_DEFAULT && num_envs <= 4096);
+    const char* nf = getenv("ZB_DIAG_NO_FINALIZE");
+    h->diag_no_finalize = nf && nf[0] == '1' && nf[1] == 0;
   }
+  rc = allocate(h, m);
+  if (!rc) rc = construction_reset(h);
+  if (!rc && kTasks[h->task].side) rc = kTasks[h->task].side(h, m);
+  if (rc) return rc;
   HIPCHK(hipDeviceSynchronize(), "zb_create sync");
+  own.h = nullptr;  // success: the caller owns the handle
   *out = h;
   return 0;
 }
@@ -5215,60 +4491,49 @@ int zb_profile_end(zb_handle h, float* total_ms, int* count) {
   return 0;
 }
 
-// Diagnostic build only (-DZB_STAMPS): the phase cycles of the slowest wave since the last reset.
-int zb_read_stamps_slowest(uint64_t* out16) {
+// Diagnostic build only (-DZB_STAMPS); the product build refuses each reader.
 #ifdef ZB_STAMPS
+// the phase cycles of the slowest wave since the last reset
+int zb_read_stamps_slowest(uint64_t* out16) {
   unsigned long long tmp[NSTAMP];
   HIPCHK(hipMemcpyFromSymbol(tmp, HIP_SYMBOL(g_stamp_slowest), sizeof(tmp)), "hipMemcpyFromSymbol");
   for (int k = 0; k < 16; ++k) out16[k] = k < NSTAMP ? tmp[k] : 0;
   return 0;
-#else
-  (void)out16;
-  return set_err(-1, "zb_read_stamps_slowest: library built without -DZB_STAMPS", hipSuccess);
-#endif
 }
 
-// Diagnostic build only (-DZB_STAMPS): per-phase cycle sums over all waves since the last call.
+// per-phase cycle sums over all waves since the last call
 int zb_read_stamp_hist(uint64_t* out136) {
-  uint64_t* out128 = out136;
-#ifdef ZB_STAMPS
   unsigned long long tmp[kCapCounters + 8];
   HIPCHK(hipMemcpyFromSymbol(tmp, HIP_SYMBOL(g_stamp_hist), sizeof(tmp)), "hipMemcpyFromSymbol");
-  for (int k = 0; k < kCapCounters + 8; ++k) out128[k] = tmp[k];
+  for (int k = 0; k < kCapCounters + 8; ++k) out136[k] = tmp[k];
   unsigned long long z[kCapCounters + 8] = {0};
   HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_hist), z, sizeof(z)), "hipMemcpyToSymbol");
   return 0;
-#else
-  (void)out128;
-  return set_err(-1, "zb_read_stamp_hist: library built without -DZB_STAMPS", hipSuccess);
-#endif
 }
-// Diagnostic build only (-DZB_STAMPS): per workgroup of the latest step launch {start, end}
-// (s_memrealtime ticks, 100 MHz) and its 13 phase cycle counts; n workgroups.
+
+// per workgroup of the latest step launch {start, end} (s_memrealtime ticks, 100 MHz) and its 13 phase cycle
+// counts; n workgroups
 int zb_read_wave_times(uint64_t* out, int n) {
-#ifdef ZB_STAMPS
   if (!out || n < 0 || n > kMaxWaveRecs) return set_err(-1, "zb_read_wave_times", hipSuccess);
   HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_rec), sizeof(unsigned long long) * kWaveRec * (size_t)n),
          "hipMemcpyFromSymbol");
   return 0;
-#else
-  (void)out; (void)n;
-  return set_err(-1, "zb_read_wave_times: library built without -DZB_STAMPS", hipSuccess);
-#endif
 }
+
 int zb_read_stamps(uint64_t* out16) {
-#ifdef ZB_STAMPS
   unsigned long long tmp[NSTAMP];
   HIPCHK(hipMemcpyFromSymbol(tmp, HIP_SYMBOL(g_stamps), sizeof(tmp)), "hipMemcpyFromSymbol");
   for (int k = 0; k < 16; ++k) out16[k] = k < NSTAMP ? tmp[k] : 0;
   unsigned long long z[NSTAMP] = {0};
   HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)), "hipMemcpyToSymbol");
   return 0;
-#else
-  (void)out16;
-  return set_err(-1, "zb_read_stamps: library built without -DZB_STAMPS", hipSuccess);
-#endif
 }
+#else
+int zb_read_stamps_slowest(uint64_t*) { return set_err(-1, "zb_read_stamps_slowest: library built without -DZB_STAMPS", hipSuccess); }
+int zb_read_stamp_hist(uint64_t*) { return set_err(-1, "zb_read_stamp_hist: library built without -DZB_STAMPS", hipSuccess); }
+int zb_read_wave_times(uint64_t*, int) { return set_err(-1, "zb_read_wave_times: library built without -DZB_STAMPS", hipSuccess); }
+int zb_read_stamps(uint64_t*) { return set_err(-1, "zb_read_stamps: library built without -DZB_STAMPS", hipSuccess); }
+#endif
 
 void zb_destroy(zb_handle h) {
   if (!h) return;
@@ -5316,13 +4581,8 @@ int zb_reset(zb_handle h, const int32_t* env_ids, int n, void* stream) {
   if (cnt <= 0) return 0;
   kTasks[h->task].reset(h, env_ids, cnt, s, 0);
   int rc = launch_check("zb_reset_kernel");
-  if (rc) return rc;
-  if (h->d_wc) {
-    zb_wc_fill_kernel<<<(cnt * ZB_WARM_ROWS + 255) / 256, 256, 0, s>>>(h->n, h->d_wc, env_ids, cnt);
-    rc = launch_check("zb_wc_fill_kernel");
-    if (rc) return rc;
-  }
-  rc = finalize(h, s, env_ids == nullptr || n == h->n, 1, 0);
+  if (!rc) rc = wc_fill(h, env_ids, cnt, s);
+  if (!rc) rc = finalize(h, s, env_ids == nullptr || n == h->n, 1, 0);
   if (rc || !h->u_critic) return rc;
   return critic_obs(h, h->u_critic, s);
 }
@@ -5390,13 +4650,8 @@ int zb_set_link_friction_sd(zb_handle h, const float* mu_static, const float* mu
   const TaskRow& row = kTasks[h->task];
   if (row.mu_row < 0)
     return set_err(-1, "zb_set_link_friction: per-link friction is a standup / manager task state", hipSuccess);
-  zb_su_friction_kernel<<<(h->n * NL + 255) / 256, 256, 0, (hipStream_t)stream>>>(
-      h->n, h->d_state, mu_static, 0.f, row.mu_row);
-  int rc = launch_check("zb_su_friction_kernel");
-  if (rc) return rc;
-  zb_su_friction_kernel<<<(h->n * NL + 255) / 256, 256, 0, (hipStream_t)stream>>>(
-      h->n, h->d_state, mu_dynamic, 0.f, row.mud_row);
-  return launch_check("zb_su_friction_kernel");
+  const int rc = friction_rows(h, mu_static, 0.f, row.mu_row, (hipStream_t)stream);
+  return rc ? rc : friction_rows(h, mu_dynamic, 0.f, row.mud_row, (hipStream_t)stream);
 }
 
 int zb_set_link_friction(zb_handle h, const float* mu, void* stream) {
@@ -5468,18 +4723,12 @@ int zb_manager_event_state_dim(zb_handle h) { return h && h->task == ZB_TASK_MAN
 
 int zb_get_manager_event_state(zb_handle h, float* dst, void* stream) {
   if (!h || !dst || !h->d_ev) return set_err(-1, "zb_get_manager_event_state (a manager-task handle)", hipSuccess);
-  HIPCHK(hipMemcpyAsync(dst, h->d_ev, sizeof(float) * ZB_ME_STATE_DIM * (size_t)h->n, hipMemcpyDeviceToDevice,
-                        (hipStream_t)stream),
-         "hipMemcpyAsync event state");
-  return 0;
+  return copy_rows(dst, h->d_ev, ZB_ME_STATE_DIM, h, stream, "hipMemcpyAsync event state");
 }
 
 int zb_set_manager_event_state(zb_handle h, const float* src, void* stream) {
   if (!h || !src || !h->d_ev) return set_err(-1, "zb_set_manager_event_state (a manager-task handle)", hipSuccess);
-  HIPCHK(hipMemcpyAsync(h->d_ev, src, sizeof(float) * ZB_ME_STATE_DIM * (size_t)h->n, hipMemcpyDeviceToDevice,
-                        (hipStream_t)stream),
-         "hipMemcpyAsync event state");
-  return 0;
+  return copy_rows(h->d_ev, src, ZB_ME_STATE_DIM, h, stream, "hipMemcpyAsync event state");
 }
 
 int zb_set_manager_terms(zb_handle h, const zb_manager_terms* tc, void* stream) {
@@ -5502,8 +4751,7 @@ int zb_set_manager_terms(zb_handle h, const zb_manager_terms* tc, void* stream) 
   h->tm_on = tc->active != 0u;
   HIPCHK(hipMemsetAsync(h->d_tm, 0, sizeof(float) * ZB_MT_STATE_DIM * (size_t)h->n, (hipStream_t)stream), "hipMemsetAsync term state");
   zb_m_terms_cfg_kernel<<<1, 1, 0, (hipStream_t)stream>>>(h->tm, h->d_tmc);
-  if (launch_check("zb_m_terms_cfg_kernel")) return -1;
-  return 0;
+  return launch_check("zb_m_terms_cfg_kernel");
 }
 
 int zb_manager_terms_active(zb_handle h) { return h && h->tm_on ? 1 : 0; }
@@ -5529,10 +4777,7 @@ int zb_get_manager_terms_state(zb_handle h, float* dst, void* stream) {
 
 int zb_set_manager_terms_state(zb_handle h, const float* src, void* stream) {
   if (!h || !src || !h->d_tm) return set_err(-1, "zb_set_manager_terms_state (a manager-task handle)", hipSuccess);
-  HIPCHK(hipMemcpyAsync(h->d_tm, src, sizeof(float) * ZB_MT_STATE_DIM * (size_t)h->n, hipMemcpyDeviceToDevice,
-                        (hipStream_t)stream),
-         "hipMemcpyAsync term state");
-  return 0;
+  return copy_rows(h->d_tm, src, ZB_MT_STATE_DIM, h, stream, "hipMemcpyAsync term state");
 }
 
 int zb_set_base_link(zb_handle h, const zb_base_link* link) {
@@ -5600,38 +4845,24 @@ int zb_set_log_accumulator(zb_handle h, float* acc) {
 
 int zb_get_state(zb_handle h, float* dst, void* stream) {
   if (!h || !dst) return set_err(-1, "zb_get_state", hipSuccess);
-  HIPCHK(hipMemcpyAsync(dst, h->d_state, sizeof(float) * (size_t)h->state_dim * h->n, hipMemcpyDeviceToDevice,
-                        (hipStream_t)stream),
-         "hipMemcpyAsync state");
-  return 0;
+  return copy_rows(dst, h->d_state, h->state_dim, h, stream, "hipMemcpyAsync state");
 }
 
 int zb_set_state(zb_handle h, const float* src, void* stream) {
   if (!h || !src) return set_err(-1, "zb_set_state", hipSuccess);
-  HIPCHK(hipMemcpyAsync(h->d_state, src, sizeof(float) * (size_t)h->state_dim * h->n, hipMemcpyDeviceToDevice,
-                        (hipStream_t)stream),
-         "hipMemcpyAsync state");
-  if (h->d_wc) {  // a new state: no warm start from the old one's contacts
-    zb_wc_fill_kernel<<<(h->n * ZB_WARM_ROWS + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->n, h->d_wc, nullptr, h->n);
-    return launch_check("zb_wc_fill_kernel");
-  }
-  return 0;
+  const int rc = copy_rows(h->d_state, src, h->state_dim, h, stream, "hipMemcpyAsync state");
+  // a new state: no warm start from the old one's contacts
+  return rc ? rc : wc_fill(h, nullptr, h->n, (hipStream_t)stream);
 }
 
 int zb_get_contact_cache(zb_handle h, float* dst, void* stream) {
   if (!h || !dst || !h->d_wc) return set_err(-1, "zb_get_contact_cache", hipSuccess);
-  HIPCHK(hipMemcpyAsync(dst, h->d_wc, sizeof(float) * ZB_WARM_ROWS * (size_t)h->n, hipMemcpyDeviceToDevice,
-                        (hipStream_t)stream),
-         "hipMemcpyAsync contact cache");
-  return 0;
+  return copy_rows(dst, h->d_wc, ZB_WARM_ROWS, h, stream, "hipMemcpyAsync contact cache");
 }
 
 int zb_set_contact_cache(zb_handle h, const float* src, void* stream) {
   if (!h || !src || !h->d_wc) return set_err(-1, "zb_set_contact_cache", hipSuccess);
-  HIPCHK(hipMemcpyAsync(h->d_wc, src, sizeof(float) * ZB_WARM_ROWS * (size_t)h->n, hipMemcpyDeviceToDevice,
-                        (hipStream_t)stream),
-         "hipMemcpyAsync contact cache");
-  return 0;
+  return copy_rows(h->d_wc, src, ZB_WARM_ROWS, h, stream, "hipMemcpyAsync contact cache");
 }
 
 int zb_physics_substeps(zb_handle h, const float* targets, int nsub, float* net_force, float* applied_torque,
@@ -5640,28 +4871,30 @@ int zb_physics_substeps(zb_handle h, const float* targets, int nsub, float* net_
   const int blocks = (h->n + EPW - 1) / EPW;
   const bool dr = h->task == ZB_TASK_STANDUP_V0 || h->task == ZB_TASK_MANAGER_V0, tgs = h->cfg.solver_mode >= 1;
   const bool refresh = h->cfg.solver_mode >= 2;
-#define ZB_SUB(F, T, R) zb_substeps_kernel<F, T, R><<<blocks, WGT, 0, (hipStream_t)stream>>>(h->d_model, h->d_links, \
-                                                 h->cfg, h->n, h->d_state, targets, nsub, net_force, applied_torque)
-  if (h->bi_on) {  // (manager task: no refresh; zb_create)
-    if (tgs) zb_bi_substeps_kernel<true><<<blocks, WGT, 0, (hipStream_t)stream>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state,
-                                                                                 targets, nsub, net_force, applied_torque, h->d_bi);
-    else zb_bi_substeps_kernel<false><<<blocks, WGT, 0, (hipStream_t)stream>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state,
-                                                                               targets, nsub, net_force, applied_torque, h->d_bi);
-  } else if (dr) {
-    if (refresh) ZB_SUB(true, true, true);
-    else if (tgs) ZB_SUB(true, true, false);
-    else ZB_SUB(true, false, false);
-  } else {
-    if (refresh) ZB_SUB(false, true, true);
-    else if (tgs) ZB_SUB(false, true, false);
-    else ZB_SUB(false, false, false);
-  }
-#undef ZB_SUB
+  hipStream_t s = (hipStream_t)stream;
+  using T = std::true_type;
+  using N = std::false_type;
+  // <kDr, kTgs, kRefresh> as integral constants (the refresh always with kTgs), as with_variant does
+  auto sub = [&](auto kDr, auto kTgs, auto kRefresh) {
+    zb_substeps_kernel<kDr.value, kTgs.value, kRefresh.value><<<blocks, WGT, 0, s>>>(
+        h->d_model, h->d_links, h->cfg, h->n, h->d_state, targets, nsub, net_force, applied_torque);
+  };
+  auto mode = [&](auto kDr) {
+    if (refresh) sub(kDr, T{}, T{});
+    else if (tgs) sub(kDr, T{}, N{});
+    else sub(kDr, N{}, N{});
+  };
+  auto bi = [&](auto kTgs) {  // (manager task: no refresh; zb_create)
+    zb_bi_substeps_kernel<kTgs.value><<<blocks, WGT, 0, s>>>(h->d_model, h->d_links, h->cfg, h->n, h->d_state, targets, nsub,
+                                                             net_force, applied_torque, h->d_bi);
+  };
+  if (h->bi_on && tgs) bi(T{});
+  else if (h->bi_on) bi(N{});
+  else if (dr) mode(T{});
+  else mode(N{});
   const int rc = launch_check("zb_substeps_kernel");
-  if (rc || !h->d_wc) return rc;
   // the physics moved: the self-contact cache describes another state (cold start next step)
-  zb_wc_fill_kernel<<<(h->n * ZB_WARM_ROWS + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->n, h->d_wc, nullptr, h->n);
-  return launch_check("zb_wc_fill_kernel");
+  return rc ? rc : wc_fill(h, nullptr, h->n, s);
 }
 
 int zb_pair_manifold_mode(const float* pairs, int n, float margin, int mode, float* out, void* stream) {
