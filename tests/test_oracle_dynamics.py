@@ -72,10 +72,13 @@ def reference(name, cfg, mutant=None, base="model", round_model=False):
                        round_model=round_model)
 
 
-def oracle_substeps(name, cfg, rows, targets, nsubs=(1, 4), double=True, f64_model=True):
+def oracle_substeps(name, cfg, rows, targets, nsubs=(1, 4), double=True, f64_model=True, state_rows=None, forces=None):
     """The physics rows after each of ``nsubs`` substeps (cumulative) and the applied torque of the last
     call, from the C oracle on ``oracle_robot(name)``; the f64 build with the model rows in double unless
-    ``f64_model`` is off (then it reads pack_model's float32 rows, as the f32 oracle and the device do)."""
+    ``f64_model`` is off (then it reads pack_model's float32 rows, as the f32 oracle and the device do).
+    ``state_rows`` {first row: [k, n] array} fills further state rows (the per-link friction of the
+    stand-up and manager tasks); ``forces``: a dict that receives, per entry of ``nsubs``, the per-link
+    net contact force [n, 12, 3] of that call's last substep."""
     from oracle import pyoracle
     lib = pyoracle.lib(double)
     rm = oracle_robot(name)
@@ -87,6 +90,8 @@ def oracle_substeps(name, cfg, rows, targets, nsubs=(1, 4), double=True, f64_mod
             pyoracle.set_model_f64(lib, h, rm)
         st = np.zeros((cfg.state_dim, n), np.float32)
         st[:NPHYS] = rows
+        for first, block in (state_rows or {}).items():
+            st[first:first + len(block)] = block
         lib.zbo_set_state(h, st)
         out, done = {}, 0
         at = np.zeros((n, ND), np.float32)
@@ -95,7 +100,11 @@ def oracle_substeps(name, cfg, rows, targets, nsubs=(1, 4), double=True, f64_mod
             sep = np.zeros(n, np.float32)
             lib.zbo_self_min_sep(h, sep)
             seps.append(sep)
-            lib.zbo_physics_substeps(h, np.ascontiguousarray(targets, np.float32), k - done, None, at.ctypes.data_as(C.c_void_p))
+            nf = np.zeros((n, zm.NUM_LINKS, 3), np.float32)
+            lib.zbo_physics_substeps(h, np.ascontiguousarray(targets, np.float32), k - done,
+                                     nf.ctypes.data_as(C.c_void_p) if forces is not None else None, at.ctypes.data_as(C.c_void_p))
+            if forces is not None:
+                forces[k] = nf
             done = k
             got = np.zeros_like(st)
             lib.zbo_get_state(h, got)
